@@ -15,6 +15,12 @@ GPU-resident state; the (-old,+new) count deltas are emitted.
 
 Driver contract: --gpus N --steps K --warmup W; launched via torchrun for
 N>1 (one rank per GPU, RCCL); rank 0 prints ONE json line.
+
+A plain run does only what the headline figure needs: set up, warm up,
+time the K steps, print the line.  --dump-outputs DIR additionally writes
+the output deltas of the last timed step as DIR/<name>.npy (inputs are
+seeded, so two builds can be compared array for array).  --full adds the
+p50 RAG latency probe (config.rag_*), which takes a run of its own.
 """
 
 from __future__ import annotations
@@ -101,6 +107,61 @@ def measure_rag_p50(device, *, n_docs: int = 100_000, n_queries: int = 128,
     }
 
 
+DUMP_BYTE_CAP = 64 * 1024 * 1024
+
+
+def _int_words(t: torch.Tensor) -> torch.Tensor:
+    """int64 (n, ...) -> float64 (n, ..., 2) of (high, low) unsigned 32-bit
+    words: exact in float64, unlike a direct cast of a 64-bit hash."""
+    t = t.to(torch.int64).cpu()
+    hi = (t >> 32) & 0xFFFFFFFF
+    lo = t & 0xFFFFFFFF
+    return torch.stack([hi, lo], dim=-1).to(torch.float64).reshape(t.shape[0], -1)
+
+
+def dump_outputs(out_dir: str, batches: list, suffix: str = "") -> None:
+    """Write the deltas the sink received in the last timed step.
+
+    One float64 array per field, rows in the order the writer got them:
+      keys   (n, 4)  128-bit row key as four 32-bit words
+      diffs  (n,)    -1 retraction / +1 insertion
+      word   (n,)    dictionary code of the word (index into the vocab)
+      count  (n,)    the new (or retracted) count
+    Above DUMP_BYTE_CAP in total, a fixed seeded sample of the rows is kept
+    (same rows in every run with the same arguments).  With several ranks
+    each writes its own shard as <name><suffix>.npy."""
+    import numpy as np
+
+    from pathway_amd.engine.batch import DeltaBatch
+    from pathway_amd.engine.column import PointerColumn, StringColumn, TensorColumn
+
+    assert batches, "--dump-outputs: the timed path emitted nothing in its last step"
+    b = DeltaBatch.concat(batches)
+    arrays = {
+        "keys": _int_words(b.keys),
+        "diffs": b.diffs.cpu().to(torch.float64),
+    }
+    for name, col in b.columns.items():
+        if isinstance(col, StringColumn):
+            arrays[name] = col.codes.cpu().to(torch.float64)
+        elif isinstance(col, PointerColumn):
+            arrays[name] = _int_words(col.pairs)
+        elif isinstance(col, TensorColumn):
+            arrays[name] = col.tensor.cpu().to(torch.float64)
+        else:
+            raise TypeError(f"--dump-outputs: cannot dump column {name!r} ({type(col).__name__})")
+    n = len(b)
+    row_bytes = sum(a[0].numel() * 8 for a in arrays.values()) if n else 0
+    if n * row_bytes > DUMP_BYTE_CAP:
+        keep = DUMP_BYTE_CAP // row_bytes
+        idx = np.sort(np.random.default_rng(2024).choice(n, size=keep, replace=False))
+        sel = torch.from_numpy(idx)
+        arrays = {k: a.index_select(0, sel) for k, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a.numpy())
+
+
 def main() -> None:
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
@@ -120,6 +181,18 @@ def main() -> None:
         default="bytes",
         help="codes: pre-parsed dictionary codes; bytes: raw newline-separated "
         "byte stream tokenized+hashed on-device (HIP varlen kernel)",
+    )
+    p.add_argument(
+        "--dump-outputs",
+        metavar="DIR",
+        default=None,
+        help="after the timed steps, write the last step's output deltas "
+        "as DIR/<name>.npy (float64)",
+    )
+    p.add_argument(
+        "--full",
+        action="store_true",
+        help="also run the p50 RAG query latency probe (config.rag_*)",
     )
     args = p.parse_args()
 
@@ -361,9 +434,13 @@ def main() -> None:
         )
 
     emitted = [0]
+    last_out: list = []  # batches delivered at the most recent timestamp
 
     def counting_writer(batch):
         emitted[0] += len(batch)
+        if last_out and last_out[0].time != batch.time:
+            last_out.clear()
+        last_out.append(batch)
 
     sink = OutputNode(counts._node, counting_writer, device)
     rt = Runtime([sink], device=device, comm=comm)
@@ -424,10 +501,23 @@ def main() -> None:
         dist.all_reduce(et, op=dist.ReduceOp.MAX)
         elapsed = float(et.item())
 
+    if args.dump_outputs:
+        dump_outputs(
+            args.dump_outputs,
+            [b for b in last_out if b.time == t - 2] if args.steps > 0 else [],
+            suffix=f"_rank{rank}" if world > 1 else "",
+        )
+
     # second half of the BASELINE metric: p50 RAG latency at fixed QPS
-    # (measured on rank 0 after the timed wordcount region; single GPU)
+    # (--full only; measured on rank 0 after the timed wordcount region;
+    # single GPU)
     rag_stats: dict = {}
-    if use_cuda and rank == 0 and not os.environ.get("PW_NO_RAG_BENCH"):
+    if (
+        args.full
+        and use_cuda
+        and rank == 0
+        and not os.environ.get("PW_NO_RAG_BENCH")
+    ):
         try:
             rag_stats = measure_rag_p50(device)
         except Exception as e:  # never fail the headline on the rag probe
