@@ -59,6 +59,12 @@ import os as _os
 #: PW_NO_SEGRED=1 falls back to the torch boundary chain (A/B)
 _PW_NO_SEGRED = bool(_os.environ.get("PW_NO_SEGRED"))
 
+#: group combine (pw_gc_*: rocPRIM sort on the interleaved keys + reduce
+#: through the permutation) inside the seg-reduce branch — default ON;
+#: PW_NO_GROUP_COMBINE=1 forces the lex_sort_words/gather_all/seg_reduce
+#: chain (A/B)
+_PW_NO_GROUP_COMBINE = bool(_os.environ.get("PW_NO_GROUP_COMBINE"))
+
 #: opt-in HIP hash-aggregation pre-agg (PW_HASHAGG=1). Measured on MI355X:
 #: the sort path wins at both 50k-distinct (2.95 vs 3.63 ms/step — atomic
 #: contention on hot counters) and 50M-distinct (sort savings vanish when
@@ -606,18 +612,30 @@ class GroupReduceNode(Node):
                 # run-starts/compaction/per-acc-sum chain in two kernels
                 from pathway_amd import ops
 
-                words = [gkeys[:, 0].contiguous(), gkeys[:, 1].contiguous()]
-                perm = lex_sort_words(words)
                 names = list(contribs)
-                sw0, sw1, *sc_list = ops.gather_all(
-                    perm, words + [contribs[nm] for nm in names]
-                )
-                uk0, uk1, first_sorted, accs = ops.seg_reduce_gpu(
-                    sw0, sw1, sc_list
-                )
+                if (
+                    not _PW_NO_GROUP_COMBINE
+                    and len(names) <= 8
+                    and 2048 < gkeys.shape[0] < 2**32
+                ):
+                    # interleaved keys straight through to reduced output
+                    # (pw_gc_*): no de-stacked key copy, no sorted copies
+                    # of the words or the contributions
+                    uk0, uk1, gfirst_rows, accs = ops.group_combine_gpu(
+                        gkeys, [contribs[nm] for nm in names]
+                    )
+                else:
+                    words = [gkeys[:, 0].contiguous(), gkeys[:, 1].contiguous()]
+                    perm = lex_sort_words(words)
+                    sw0, sw1, *sc_list = ops.gather_all(
+                        perm, words + [contribs[nm] for nm in names]
+                    )
+                    uk0, uk1, first_sorted, accs = ops.seg_reduce_gpu(
+                        sw0, sw1, sc_list
+                    )
+                    gfirst_rows = perm.index_select(0, first_sorted)
                 ukeys_w = [uk0, uk1]
                 acc_deltas = dict(zip(names, accs))
-                gfirst_rows = perm.index_select(0, first_sorted)
                 gcols_first = {
                     n: c.take(gfirst_rows) for n, c in gcols.items()
                 }

@@ -430,6 +430,89 @@ def seg_reduce_gpu(
     return out_words[0], out_words[1], out_first, out_accs
 
 
+#: rocPRIM temp-storage bytes of the group-combine sort, per row count
+_gc_temp_bytes: dict[int, int] = {}
+
+
+def group_combine_gpu(
+    keys_n2: torch.Tensor, contribs: Sequence[torch.Tensor]
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, list]:
+    """The groupby combiner on UNSORTED interleaved keys: (n,2) int64 keys
+    + up to 8 int64 contribution columns -> (uk0, uk1, first_row, accs)
+    with unique keys in signed lexicographic order, per-key sums and the
+    smallest input row of every key (pw_gc_*: rocPRIM sort of word0 with a
+    32-bit row-index payload read straight from the interleaved rows, one
+    word1 gather + repair, then a segmented reduce that reads the
+    contributions through the permutation).  One host sync (segment
+    count)."""
+    lib = require_lib()
+    n = keys_n2.shape[0]
+    dev = keys_n2.device
+    nacc = len(contribs)
+    assert keys_n2.dim() == 2 and keys_n2.shape[1] == 2
+    assert keys_n2.dtype == torch.int64
+    assert 2 <= n < 2**32 and nacc <= 8
+    if keys_n2.stride() != (2, 1):
+        keys_n2 = keys_n2.contiguous()
+    contribs = [c.contiguous() for c in contribs]
+    assert all(c.dtype == torch.int64 and c.shape == (n,) for c in contribs)
+    tbytes = _gc_temp_bytes.get(n)
+    if tbytes is None:
+        lib.pw_gc_temp_bytes.restype = ctypes.c_int64
+        tbytes = int(lib.pw_gc_temp_bytes(ctypes.c_int64(n)))
+        if tbytes <= 0:
+            raise RuntimeError("pw_gc_temp_bytes failed")
+        _gc_temp_bytes[n] = tbytes
+    temp = torch.empty(tbytes, dtype=torch.uint8, device=dev)
+    sorted_k = torch.empty((2, n), dtype=torch.int64, device=dev)
+    perm32 = torch.empty(n, dtype=torch.int32, device=dev)  # uint32 bits
+    nblocks = (n + 255) // 256
+    block_counts = torch.empty(nblocks, dtype=torch.int32, device=dev)
+    stream = _stream_ptr()
+    rc = lib.pw_gc_sort_count(
+        ctypes.c_void_p(keys_n2.data_ptr()),
+        ctypes.c_int64(n),
+        ctypes.c_void_p(temp.data_ptr()),
+        ctypes.c_int64(tbytes),
+        ctypes.c_void_p(sorted_k[0].data_ptr()),
+        ctypes.c_void_p(sorted_k[1].data_ptr()),
+        ctypes.c_void_p(perm32.data_ptr()),
+        ctypes.c_int(4),
+        ctypes.c_void_p(block_counts.data_ptr()),
+        stream,
+    )
+    if rc != 0:
+        raise RuntimeError(f"pw_gc_sort_count failed: hip error {rc}")
+    csum = torch.cumsum(block_counts, 0, dtype=torch.int64)
+    nseg = int(csum[-1].item())
+    out_k = torch.empty((2, nseg), dtype=torch.int64, device=dev)
+    out_first = torch.empty(nseg, dtype=torch.int64, device=dev)
+    out_accs = torch.zeros((max(nacc, 1), nseg), dtype=torch.int64, device=dev)
+    carr = (ctypes.c_void_p * max(nacc, 1))(
+        *[ctypes.c_void_p(c.data_ptr()) for c in contribs]
+    )
+    oarr = (ctypes.c_void_p * max(nacc, 1))(
+        *[ctypes.c_void_p(out_accs[a].data_ptr()) for a in range(nacc)]
+    )
+    rc = lib.pw_gc_emit(
+        ctypes.c_void_p(sorted_k[0].data_ptr()),
+        ctypes.c_void_p(sorted_k[1].data_ptr()),
+        ctypes.c_void_p(perm32.data_ptr()),
+        carr,
+        ctypes.c_int(nacc),
+        ctypes.c_int64(n),
+        ctypes.c_void_p(csum.data_ptr()),
+        ctypes.c_void_p(out_k[0].data_ptr()),
+        ctypes.c_void_p(out_k[1].data_ptr()),
+        ctypes.c_void_p(out_first.data_ptr()),
+        oarr,
+        stream,
+    )
+    if rc != 0:
+        raise RuntimeError(f"pw_gc_emit failed: hip error {rc}")
+    return out_k[0], out_k[1], out_first, [out_accs[a] for a in range(nacc)]
+
+
 def partition_gpu(dest: torch.Tensor, world: int) -> tuple[torch.Tensor, torch.Tensor]:
     """Radix partition by destination rank: returns (perm, counts) with rows
     grouped by destination (exchange shuffle pack; pact.rs:56 analog)."""

@@ -15,6 +15,9 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <cstring>  // rocprim.hpp uses std::memcpy without including it
+#include <rocprim/rocprim.hpp>
+
 #include "../xxhash_common.h"
 
 #define PW_BLOCK 256
@@ -1713,5 +1716,187 @@ extern "C" int pw_gather_cols(const void* idx, int64_t m, int ncols,
   if (nblocks < 1) nblocks = 1;
   hipLaunchKernelGGL(k_gather_cols, dim3((uint32_t)nblocks), dim3(PW_BLOCK),
                      0, s, (const long long*)idx, m, ncols, p);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------- group combine --
+// The groupby combiner on interleaved (n,2) int64 keys, start to finish:
+// rows of (key128, contributions...) -> (unique key, sums, first row).
+//
+//   sort     rocprim::radix_sort_pairs over word0, read in place from the
+//            16-byte rows through a transform iterator; the payload is a
+//            32-bit row index from a counting iterator (12 B/row per
+//            onesweep pass instead of torch.sort's 16, no arange, no
+//            de-stacked key copy)
+//   gather   k_gc_gather_k1: word1 through the permutation, once
+//   repair   k_gc_sort_repair: k_sort_repair on a uint32 permutation
+//   count    k_segred_count, as is
+//   emit     k_gc_emit: k_segred_emit reading the contributions THROUGH
+//            the permutation (no sorted contribution column is written)
+//            and emitting the original row id of each segment start
+//
+// The sort is stable and the repair swaps only strictly out-of-order
+// word1 pairs, so equal keys keep ascending row order and a segment's
+// first row is its smallest row index.  Signed int64 key order (rocPRIM
+// flips the sign bit for signed key types), matching the state's order.
+
+struct GcWord0 {
+  const long long* keys;  // (n,2) row-major
+  __host__ __device__ long long operator()(uint32_t i) const {
+    return keys[2 * (size_t)i];
+  }
+};
+
+using GcKeyIter =
+    rocprim::transform_iterator<rocprim::counting_iterator<uint32_t>, GcWord0,
+                                long long>;
+
+static hipError_t gc_sort(void* temp, size_t& temp_bytes, const long long* keys,
+                          long long* k0_sorted, uint32_t* perm32, int64_t n,
+                          hipStream_t s) {
+  GcKeyIter kin(rocprim::counting_iterator<uint32_t>(0), GcWord0{keys});
+  rocprim::counting_iterator<uint32_t> vin(0);
+  return rocprim::radix_sort_pairs(temp, temp_bytes, kin, k0_sorted, vin,
+                                   perm32, (size_t)n, 0, 64, s);
+}
+
+__global__ void k_gc_gather_k1(const long long* __restrict__ keys,
+                               const uint32_t* __restrict__ perm32,
+                               long long* __restrict__ k1_sorted, int64_t n) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (; i < n; i += stride) k1_sorted[i] = keys[2 * (size_t)perm32[i] + 1];
+}
+
+__global__ void k_gc_sort_repair(const long long* __restrict__ k0,
+                                 long long* k1, uint32_t* perm32, int64_t n,
+                                 int parity) {
+  int64_t i = 2 * ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) + parity;
+  if (i + 1 >= n) return;
+  if (k0[i] != k0[i + 1]) return;
+  long long a = k1[i], b = k1[i + 1];
+  if (a > b) {
+    k1[i] = b;
+    k1[i + 1] = a;
+    uint32_t p = perm32[i];
+    perm32[i] = perm32[i + 1];
+    perm32[i + 1] = p;
+  }
+}
+
+// block_csum is the INCLUSIVE prefix sum of k_segred_count's block counts
+__global__ void k_gc_emit(const long long* __restrict__ k0,
+                          const long long* __restrict__ k1,
+                          const uint32_t* __restrict__ perm32,
+                          AccPtrs contribs, int nacc, int64_t n,
+                          const long long* __restrict__ block_csum,
+                          long long* out_k0, long long* out_k1,
+                          long long* out_first, AccPtrsMut out_accs) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int lane = threadIdx.x & 63;
+  int flag = 0;
+  long long a0 = 0, a1 = 0;
+  uint32_t row = 0;
+  if (i < n) {
+    a0 = k0[i];
+    a1 = k1[i];
+    row = perm32[i];
+    flag = (i == 0) || a0 != k0[i - 1] || a1 != k1[i - 1];
+  }
+  // block-wide exclusive scan of flags via per-wave ballot + LDS
+  uint64_t ball = __ballot(flag);
+  int wave = threadIdx.x >> 6;
+  __shared__ int wave_tot[PW_BLOCK / 64];
+  if (lane == 0) wave_tot[wave] = __popcll(ball);
+  __syncthreads();
+  int wave_base = 0;
+  for (int j = 0; j < wave; ++j) wave_base += wave_tot[j];
+  uint64_t below = ball & ((lane == 0) ? 0ULL : ((1ULL << lane) - 1));
+  int local_excl = wave_base + __popcll(below);
+  long long base = blockIdx.x ? block_csum[blockIdx.x - 1] : 0;
+  long long sid = base + local_excl + flag - 1;
+  if (i < n && flag) {
+    out_k0[sid] = a0;
+    out_k1[sid] = a1;
+    out_first[sid] = (long long)row;
+  }
+  // wave-segmented sums per accumulator; padding lanes carry the sentinel
+  // -1 so a real row followed by padding still detects its run tail
+  long long s = (i < n) ? sid : -1;
+  long long nxt = __shfl_down(s, 1, 64);
+  bool tail = (lane == 63) || (nxt != s);
+  for (int a = 0; a < nacc; ++a) {
+    long long v = (i < n) ? contribs.p[a][row] : 0;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      long long vv = __shfl_up(v, off, 64);
+      long long ss = __shfl_up(s, off, 64);
+      if (lane >= off && ss == s) v += vv;
+    }
+    if (s >= 0 && tail)
+      atomicAdd((unsigned long long*)&out_accs.p[a][s],
+                (unsigned long long)v);
+  }
+}
+
+// bytes of rocPRIM temp storage the sort needs for n rows (0 on error)
+extern "C" int64_t pw_gc_temp_bytes(int64_t n) {
+  size_t bytes = 0;
+  if (n <= 0 || n >= ((int64_t)1 << 32)) return 0;
+  if (gc_sort(nullptr, bytes, nullptr, nullptr, nullptr, n, 0) != hipSuccess)
+    return 0;
+  return (int64_t)bytes;
+}
+
+// sort + word1 gather + repair + segment count, all on the caller's stream.
+// keys: (n,2) int64 rows 16 B apart.  Outputs: k0_sorted, k1_sorted (n
+// int64), perm32 (n uint32), block_counts (ceil(n/256) int32).
+extern "C" int pw_gc_sort_count(const void* keys, int64_t n, void* temp,
+                                int64_t temp_bytes, void* k0_sorted,
+                                void* k1_sorted, void* perm32, int passes,
+                                void* block_counts, void* stream) {
+  if (n < 2 || n >= ((int64_t)1 << 32)) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  size_t tb = (size_t)temp_bytes;
+  hipError_t e = gc_sort(temp, tb, (const long long*)keys,
+                         (long long*)k0_sorted, (uint32_t*)perm32, n, s);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(k_gc_gather_k1, dim3(2 * PW_MAX_GRID), dim3(PW_BLOCK), 0,
+                     s, (const long long*)keys, (const uint32_t*)perm32,
+                     (long long*)k1_sorted, n);
+  int64_t pairs = n / 2 + 1;
+  int64_t rblocks = (pairs + PW_BLOCK - 1) / PW_BLOCK;
+  for (int p = 0; p < passes; ++p)
+    hipLaunchKernelGGL(k_gc_sort_repair, dim3((uint32_t)rblocks),
+                       dim3(PW_BLOCK), 0, s, (const long long*)k0_sorted,
+                       (long long*)k1_sorted, (uint32_t*)perm32, n, p & 1);
+  SegWords w;
+  w.p[0] = (const int64_t*)k0_sorted;
+  w.p[1] = (const int64_t*)k1_sorted;
+  int64_t nblocks = (n + PW_BLOCK - 1) / PW_BLOCK;
+  hipLaunchKernelGGL(k_segred_count, dim3((uint32_t)nblocks), dim3(PW_BLOCK),
+                     0, s, w, 2, n, (int*)block_counts);
+  return (int)hipGetLastError();
+}
+
+extern "C" int pw_gc_emit(const void* k0_sorted, const void* k1_sorted,
+                          const void* perm32, const void** contrib_ptrs,
+                          int nacc, int64_t n, const void* block_csum,
+                          void* out_k0, void* out_k1, void* out_first,
+                          void** out_acc_ptrs, void* stream) {
+  if (nacc < 0 || nacc > 8 || n < 1) return 1;
+  AccPtrs cp;
+  AccPtrsMut op;
+  for (int a = 0; a < nacc; ++a) {
+    cp.p[a] = (const long long*)contrib_ptrs[a];
+    op.p[a] = (long long*)out_acc_ptrs[a];
+  }
+  hipStream_t s = (hipStream_t)stream;
+  int64_t nblocks = (n + PW_BLOCK - 1) / PW_BLOCK;
+  hipLaunchKernelGGL(k_gc_emit, dim3((uint32_t)nblocks), dim3(PW_BLOCK), 0, s,
+                     (const long long*)k0_sorted, (const long long*)k1_sorted,
+                     (const uint32_t*)perm32, cp, nacc, n,
+                     (const long long*)block_csum, (long long*)out_k0,
+                     (long long*)out_k1, (long long*)out_first, op);
   return (int)hipGetLastError();
 }
