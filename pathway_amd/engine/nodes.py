@@ -59,8 +59,9 @@ import os as _os
 #: PW_NO_SEGRED=1 falls back to the torch boundary chain (A/B)
 _PW_NO_SEGRED = bool(_os.environ.get("PW_NO_SEGRED"))
 
-#: group combine (pw_gc_*: rocPRIM sort on the interleaved keys + reduce
-#: through the permutation) inside the seg-reduce branch — default ON;
+#: group combine (pw_gc_*: rocPRIM sort of a 32-bit word0 prefix on the
+#: interleaved keys, prefix ties repaired on device + reduce through the
+#: permutation) inside the seg-reduce branch — default ON;
 #: PW_NO_GROUP_COMBINE=1 forces the lex_sort_words/gather_all/seg_reduce
 #: chain (A/B)
 _PW_NO_GROUP_COMBINE = bool(_os.environ.get("PW_NO_GROUP_COMBINE"))

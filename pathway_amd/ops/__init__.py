@@ -430,21 +430,77 @@ def seg_reduce_gpu(
     return out_words[0], out_words[1], out_first, out_accs
 
 
-#: rocPRIM temp-storage bytes of the group-combine sort, per row count
+#: rocPRIM temp-storage bytes of the group-combine sorts, per row count
 _gc_temp_bytes: dict[int, int] = {}
+_gc_temp_bytes_prefix: dict[int, int] = {}
+
+#: PW_GC_FULL_SORT=1 forces the 64-bit sort of word0 (A/B runs)
+_PW_GC_FULL_SORT = bool(os.environ.get("PW_GC_FULL_SORT"))
+
+#: which sort group_combine_gpu ran: the prefix sort, the 64-bit sort after
+#: the prefix path overflowed, or the 64-bit sort because it was asked for
+gc_path_counts = {"prefix": 0, "fallback": 0, "full": 0}
+
+#: prefix runs the last prefix-path call listed for repair
+gc_last_dirty_runs = 0
+
+
+def _gc_temp(lib, n: int, prefix: bool, dev) -> tuple[torch.Tensor, int]:
+    cache = _gc_temp_bytes_prefix if prefix else _gc_temp_bytes
+    tbytes = cache.get(n)
+    if tbytes is None:
+        fn = lib.pw_gc_temp_bytes_prefix if prefix else lib.pw_gc_temp_bytes
+        fn.restype = ctypes.c_int64
+        tbytes = int(fn(ctypes.c_int64(n)))
+        if tbytes <= 0:
+            raise RuntimeError("pw_gc_temp_bytes failed")
+        cache[n] = tbytes
+    return torch.empty(tbytes, dtype=torch.uint8, device=dev), tbytes
+
+
+def _group_combine_two_sorts(keys_n2, contribs):
+    """group_combine_gpu's last resort, for a batch in which more rows than
+    the repair's `max_run` share one word0 and differ in word1: two stable
+    sorts (word1, then word0), sorted copies of the contributions and
+    seg_reduce_gpu.  Same result as the other paths, at several times
+    the cost."""
+    k0, k1 = keys_n2[:, 0], keys_n2[:, 1]
+    perm = torch.argsort(k1, stable=True)
+    perm = perm.index_select(0, torch.argsort(k0.index_select(0, perm), stable=True))
+    uk0, uk1, first_sorted, accs = seg_reduce_gpu(
+        k0.index_select(0, perm),
+        k1.index_select(0, perm),
+        [c.index_select(0, perm) for c in contribs],
+    )
+    return uk0, uk1, perm.index_select(0, first_sorted), accs
 
 
 def group_combine_gpu(
-    keys_n2: torch.Tensor, contribs: Sequence[torch.Tensor]
+    keys_n2: torch.Tensor,
+    contribs: Sequence[torch.Tensor],
+    *,
+    prefix_bits: int = 32,
+    max_run: int = 2048,
+    max_dirty: int = 65536,
+    full_sort: bool = False,
 ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, list]:
     """The groupby combiner on UNSORTED interleaved keys: (n,2) int64 keys
     + up to 8 int64 contribution columns -> (uk0, uk1, first_row, accs)
     with unique keys in signed lexicographic order, per-key sums and the
-    smallest input row of every key (pw_gc_*: rocPRIM sort of word0 with a
-    32-bit row-index payload read straight from the interleaved rows, one
-    word1 gather + repair, then a segmented reduce that reads the
-    contributions through the permutation).  One host sync (segment
-    count)."""
+    smallest input row of every key (pw_gc_*: rocPRIM sort of the top
+    `prefix_bits` of word0 with a 32-bit row-index payload read straight
+    from the interleaved rows, one gather of both words, an exact repair of
+    the rows that tie on the prefix, then a segmented reduce that reads the
+    contributions through the permutation).  One host sync (segment count
+    and the repair's overflow word in one read).
+
+    A prefix run longer than `max_run` rows, or more than `max_dirty` runs
+    to repair, overflows: the batch is redone with the 64-bit sort of word0
+    (a second sync).  `full_sort` (or PW_GC_FULL_SORT=1) takes the 64-bit
+    sort at once.  That path repairs ties on the whole of word0 under the
+    same two caps; beyond them it hands over to two full sorts.  The
+    result is the same on every path."""
+    global gc_last_dirty_runs
     lib = require_lib()
     n = keys_n2.shape[0]
     dev = keys_n2.device
@@ -452,39 +508,76 @@ def group_combine_gpu(
     assert keys_n2.dim() == 2 and keys_n2.shape[1] == 2
     assert keys_n2.dtype == torch.int64
     assert 2 <= n < 2**32 and nacc <= 8
+    assert 1 <= prefix_bits <= 32 and 2 <= max_run <= 3072
+    assert 1 <= max_dirty < 2**32
     if keys_n2.stride() != (2, 1):
         keys_n2 = keys_n2.contiguous()
     contribs = [c.contiguous() for c in contribs]
     assert all(c.dtype == torch.int64 and c.shape == (n,) for c in contribs)
-    tbytes = _gc_temp_bytes.get(n)
-    if tbytes is None:
-        lib.pw_gc_temp_bytes.restype = ctypes.c_int64
-        tbytes = int(lib.pw_gc_temp_bytes(ctypes.c_int64(n)))
-        if tbytes <= 0:
-            raise RuntimeError("pw_gc_temp_bytes failed")
-        _gc_temp_bytes[n] = tbytes
-    temp = torch.empty(tbytes, dtype=torch.uint8, device=dev)
     sorted_k = torch.empty((2, n), dtype=torch.int64, device=dev)
     perm32 = torch.empty(n, dtype=torch.int32, device=dev)  # uint32 bits
     nblocks = (n + 255) // 256
     block_counts = torch.empty(nblocks, dtype=torch.int32, device=dev)
+    # block csum, then the prefix path's two control words (overflow,
+    # listed runs), so that one read fetches nseg and the overflow word
+    csum_ctrl = torch.empty(nblocks + 2, dtype=torch.int64, device=dev)
+    csum = csum_ctrl[:nblocks]
+    dirty_list = torch.empty(max_dirty, dtype=torch.int32, device=dev)
     stream = _stream_ptr()
-    rc = lib.pw_gc_sort_count(
-        ctypes.c_void_p(keys_n2.data_ptr()),
-        ctypes.c_int64(n),
-        ctypes.c_void_p(temp.data_ptr()),
-        ctypes.c_int64(tbytes),
-        ctypes.c_void_p(sorted_k[0].data_ptr()),
-        ctypes.c_void_p(sorted_k[1].data_ptr()),
-        ctypes.c_void_p(perm32.data_ptr()),
-        ctypes.c_int(4),
-        ctypes.c_void_p(block_counts.data_ptr()),
-        stream,
-    )
-    if rc != 0:
-        raise RuntimeError(f"pw_gc_sort_count failed: hip error {rc}")
-    csum = torch.cumsum(block_counts, 0, dtype=torch.int64)
-    nseg = int(csum[-1].item())
+    full_sort = full_sort or _PW_GC_FULL_SORT
+    nseg = -1
+    if not full_sort:
+        temp, tbytes = _gc_temp(lib, n, True, dev)
+        rc = lib.pw_gc_prefix_sort_count(
+            ctypes.c_void_p(keys_n2.data_ptr()),
+            ctypes.c_int64(n),
+            ctypes.c_void_p(temp.data_ptr()),
+            ctypes.c_int64(tbytes),
+            ctypes.c_void_p(sorted_k[0].data_ptr()),
+            ctypes.c_void_p(sorted_k[1].data_ptr()),
+            ctypes.c_void_p(perm32.data_ptr()),
+            ctypes.c_int(prefix_bits),
+            ctypes.c_int64(max_run),
+            ctypes.c_int64(max_dirty),
+            ctypes.c_void_p(dirty_list.data_ptr()),
+            ctypes.c_void_p(csum_ctrl[nblocks:].data_ptr()),
+            ctypes.c_void_p(block_counts.data_ptr()),
+            stream,
+        )
+        if rc != 0:
+            raise RuntimeError(f"pw_gc_prefix_sort_count failed: hip error {rc}")
+        torch.cumsum(block_counts, 0, dtype=torch.int64, out=csum)
+        nseg, overflow, gc_last_dirty_runs = csum_ctrl[nblocks - 1 :].tolist()
+        if overflow:
+            nseg = -1
+        else:
+            gc_path_counts["prefix"] += 1
+    if nseg < 0:
+        temp, tbytes = _gc_temp(lib, n, False, dev)
+        rc = lib.pw_gc_sort_count(
+            ctypes.c_void_p(keys_n2.data_ptr()),
+            ctypes.c_int64(n),
+            ctypes.c_void_p(temp.data_ptr()),
+            ctypes.c_int64(tbytes),
+            ctypes.c_void_p(sorted_k[0].data_ptr()),
+            ctypes.c_void_p(sorted_k[1].data_ptr()),
+            ctypes.c_void_p(perm32.data_ptr()),
+            ctypes.c_int(4),
+            ctypes.c_int64(max_run),
+            ctypes.c_int64(max_dirty),
+            ctypes.c_void_p(dirty_list.data_ptr()),
+            ctypes.c_void_p(csum_ctrl[nblocks:].data_ptr()),
+            ctypes.c_void_p(block_counts.data_ptr()),
+            stream,
+        )
+        if rc != 0:
+            raise RuntimeError(f"pw_gc_sort_count failed: hip error {rc}")
+        torch.cumsum(block_counts, 0, dtype=torch.int64, out=csum)
+        nseg, overflow, _ = csum_ctrl[nblocks - 1 :].tolist()
+        gc_path_counts["full" if full_sort else "fallback"] += 1
+        if overflow:
+            # thousands of rows share a whole word0 and differ in word1
+            return _group_combine_two_sorts(keys_n2, contribs)
     out_k = torch.empty((2, nseg), dtype=torch.int64, device=dev)
     out_first = torch.empty(nseg, dtype=torch.int64, device=dev)
     out_accs = torch.zeros((max(nacc, 1), nseg), dtype=torch.int64, device=dev)

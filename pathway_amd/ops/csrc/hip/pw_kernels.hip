@@ -1739,6 +1739,9 @@ extern "C" int pw_gather_cols(const void* idx, int64_t m, int ncols,
 // word1 pairs, so equal keys keep ascending row order and a segment's
 // first row is its smallest row index.  Signed int64 key order (rocPRIM
 // flips the sign bit for signed key types), matching the state's order.
+//
+// This is the full 64-bit sort.  The default is the prefix sort further
+// down; this one is its fallback and the PW_GC_FULL_SORT=1 comparison path.
 
 struct GcWord0 {
   const long long* keys;  // (n,2) row-major
@@ -1760,11 +1763,17 @@ static hipError_t gc_sort(void* temp, size_t& temp_bytes, const long long* keys,
                                    perm32, (size_t)n, 0, 64, s);
 }
 
+// ctrl: the two control words of k_gc_mark_dirty (below), cleared here
 __global__ void k_gc_gather_k1(const long long* __restrict__ keys,
                                const uint32_t* __restrict__ perm32,
-                               long long* __restrict__ k1_sorted, int64_t n) {
+                               long long* __restrict__ k1_sorted, int64_t n,
+                               unsigned long long* ctrl) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  if (i == 0) {
+    ctrl[0] = 0;
+    ctrl[1] = 0;
+  }
   for (; i < n; i += stride) k1_sorted[i] = keys[2 * (size_t)perm32[i] + 1];
 }
 
@@ -1848,14 +1857,209 @@ extern "C" int64_t pw_gc_temp_bytes(int64_t n) {
   return (int64_t)bytes;
 }
 
-// sort + word1 gather + repair + segment count, all on the caller's stream.
-// keys: (n,2) int64 rows 16 B apart.  Outputs: k0_sorted, k1_sorted (n
-// int64), perm32 (n uint32), block_counts (ceil(n/256) int32).
+// ------------------------------------------- group combine, prefix sort --
+// word0 is a 64-bit hash, so its top 32 bits already separate all but a
+// handful of keys.  The default path sorts only that prefix and mends the
+// few rows that tie on it:
+//
+//   sort     rocprim::radix_sort_pairs on a uint32 key (top prefix_bits of
+//            word0, see GcPrefix) with the uint32 row payload: four
+//            8-bit passes at 8 B/row instead of eight at 12 B/row.  The
+//            sorted keys are scratch.
+//   gather   k_gc_gather_k01: word0 and word1 through the permutation
+//   mark     k_gc_mark_dirty: lists the start of every prefix run that
+//            holds more than one distinct key; writes none of the arrays
+//   repair   k_gc_repair_runs: one block per listed run, stable rank sort
+//            of (word0, word1) in LDS, written back in place
+//   count, emit   as above
+//
+// After the repair k0_sorted, k1_sorted and perm32 are what the 64-bit
+// sort above produces: the prefix sort is stable with an ascending
+// payload, and the rank is stable, so equal keys keep ascending row order.
+// A run longer than max_run, or more than max_dirty runs, raises the
+// overflow word instead; the caller then redoes the batch with
+// pw_gc_sort_count.  ctrl[0] is that overflow word, ctrl[1] the number of
+// listed runs; the gather kernel clears both, so no memset is queued.
+
+#define PW_GC_REPAIR_GRID 64
+#define PW_GC_MAX_RUN_LIMIT 3072  // 20 B/row of LDS: 60 KB
+
+// The sort key: the top prefix_bits of word0 with the sign bit flipped
+// (unsigned order = signed int64 order), moved down to bit 0, so the sort
+// runs on bits [0, prefix_bits).  Sorting bits [32 - prefix_bits, 32) of
+// the unshifted word is the same order, but below its onesweep threshold
+// rocPRIM's merge path builds that range's mask with a 32-bit shift by 32
+// and then compares the wrong bits.
+struct GcPrefix {
+  const long long* keys;  // (n,2) row-major
+  int drop;               // 32 - prefix_bits
+  __host__ __device__ uint32_t operator()(uint32_t i) const {
+    uint32_t top = (uint32_t)((uint64_t)keys[2 * (size_t)i] >> 32);
+    return (top ^ 0x80000000u) >> drop;
+  }
+};
+
+using GcPrefixIter =
+    rocprim::transform_iterator<rocprim::counting_iterator<uint32_t>, GcPrefix,
+                                uint32_t>;
+
+static hipError_t gc_sort_prefix(void* temp, size_t& temp_bytes,
+                                 const long long* keys, uint32_t* prefix_sorted,
+                                 uint32_t* perm32, int64_t n, int prefix_bits,
+                                 hipStream_t s) {
+  GcPrefixIter kin(rocprim::counting_iterator<uint32_t>(0),
+                   GcPrefix{keys, 32 - prefix_bits});
+  rocprim::counting_iterator<uint32_t> vin(0);
+  return rocprim::radix_sort_pairs(temp, temp_bytes, kin, prefix_sorted, vin,
+                                   perm32, (size_t)n, 0u,
+                                   (unsigned int)prefix_bits, s);
+}
+
+__global__ void k_gc_gather_k01(const long long* __restrict__ keys,
+                                const uint32_t* __restrict__ perm32,
+                                long long* __restrict__ k0_sorted,
+                                long long* __restrict__ k1_sorted, int64_t n,
+                                unsigned long long* ctrl) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  if (i == 0) {
+    ctrl[0] = 0;
+    ctrl[1] = 0;
+  }
+  for (; i < n; i += stride) {
+    size_t r = 2 * (size_t)perm32[i];
+    k0_sorted[i] = keys[r];
+    k1_sorted[i] = keys[r + 1];
+  }
+}
+
+__global__ void k_gc_mark_dirty(const long long* __restrict__ k0,
+                                const long long* __restrict__ k1, int64_t n,
+                                int shift, uint32_t max_run,
+                                uint32_t max_dirty, uint32_t* dirty_list,
+                                unsigned long long* ctrl) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < 1 || i >= n) return;
+  long long c0 = k0[i], p0 = k0[i - 1];
+  uint64_t pref = (uint64_t)c0 >> shift;
+  if (((uint64_t)p0 >> shift) != pref) return;
+  long long p1 = k1[i - 1];
+  if (c0 == p0 && k1[i] == p1) return;
+  // row i is a dirty boundary.  Rows left of it equal row i-1 until the
+  // run start or an earlier dirty boundary; only the first boundary of a
+  // run lists the run.
+  int64_t j = i - 1;
+  uint32_t steps = 0;
+  while (j > 0) {
+    long long q0 = k0[j - 1];
+    if (((uint64_t)q0 >> shift) != pref) break;       // j starts the run
+    if (q0 != p0 || k1[j - 1] != p1) return;          // j is a boundary
+    --j;
+    if (++steps > max_run) {
+      ctrl[0] = 1;
+      return;
+    }
+  }
+  unsigned long long slot = atomicAdd(&ctrl[1], 1ULL);
+  if (slot < max_dirty) dirty_list[slot] = (uint32_t)j;
+  else ctrl[0] = 1;
+}
+
+__global__ void k_gc_repair_runs(long long* k0, long long* k1,
+                                 uint32_t* perm32, int64_t n, int shift,
+                                 uint32_t max_run, uint32_t max_dirty,
+                                 const uint32_t* __restrict__ dirty_list,
+                                 unsigned long long* ctrl) {
+  extern __shared__ long long gc_lds[];
+  long long* s0 = gc_lds;
+  long long* s1 = gc_lds + max_run;
+  uint32_t* sp = (uint32_t*)(gc_lds + 2 * (size_t)max_run);
+  __shared__ uint32_t run_len;
+  unsigned long long listed = ctrl[1];
+  uint32_t cnt = listed < max_dirty ? (uint32_t)listed : max_dirty;
+  for (uint32_t e = blockIdx.x; e < cnt; e += gridDim.x) {
+    int64_t s = dirty_list[e];
+    uint64_t pref = (uint64_t)k0[s] >> shift;
+    if (threadIdx.x == 0) run_len = max_run + 1;
+    __syncthreads();
+    // first row right of s, at most max_run away, that leaves the run
+    for (uint32_t r = 1 + threadIdx.x; r <= max_run; r += blockDim.x) {
+      int64_t idx = s + r;
+      if (idx >= n || ((uint64_t)k0[idx] >> shift) != pref) {
+        atomicMin(&run_len, r);
+        break;
+      }
+    }
+    __syncthreads();
+    uint32_t len = run_len;
+    if (len > max_run) {
+      if (threadIdx.x == 0) ctrl[0] = 1;
+    } else {
+      for (uint32_t t = threadIdx.x; t < len; t += blockDim.x) {
+        s0[t] = k0[s + t];
+        s1[t] = k1[s + t];
+        sp[t] = perm32[s + t];
+      }
+      __syncthreads();
+      for (uint32_t t = threadIdx.x; t < len; t += blockDim.x) {
+        long long a0 = s0[t], a1 = s1[t];
+        uint32_t rank = 0;
+        for (uint32_t u = 0; u < len; ++u) {
+          long long b0 = s0[u], b1 = s1[u];
+          bool before = b0 < a0 ||
+                        (b0 == a0 && (b1 < a1 || (b1 == a1 && u < t)));
+          rank += before ? 1u : 0u;
+        }
+        k0[s + rank] = a0;
+        k1[s + rank] = a1;
+        perm32[s + rank] = sp[t];
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// mark + repair + segment count on gathered (k0, k1, perm32)
+static int gc_repair_count(void* k0_sorted, void* k1_sorted, void* perm32,
+                           int64_t n, int shift, int64_t max_run,
+                           int64_t max_dirty, void* dirty_list, void* ctrl,
+                           void* block_counts, hipStream_t s) {
+  int64_t nblocks = (n + PW_BLOCK - 1) / PW_BLOCK;
+  hipLaunchKernelGGL(k_gc_mark_dirty, dim3((uint32_t)nblocks), dim3(PW_BLOCK),
+                     0, s, (const long long*)k0_sorted,
+                     (const long long*)k1_sorted, n, shift, (uint32_t)max_run,
+                     (uint32_t)max_dirty, (uint32_t*)dirty_list,
+                     (unsigned long long*)ctrl);
+  size_t lds = (size_t)max_run * 20;
+  hipLaunchKernelGGL(k_gc_repair_runs, dim3(PW_GC_REPAIR_GRID),
+                     dim3(PW_BLOCK), lds, s, (long long*)k0_sorted,
+                     (long long*)k1_sorted, (uint32_t*)perm32, n, shift,
+                     (uint32_t)max_run, (uint32_t)max_dirty,
+                     (const uint32_t*)dirty_list, (unsigned long long*)ctrl);
+  SegWords w;
+  w.p[0] = (const int64_t*)k0_sorted;
+  w.p[1] = (const int64_t*)k1_sorted;
+  hipLaunchKernelGGL(k_segred_count, dim3((uint32_t)nblocks), dim3(PW_BLOCK),
+                     0, s, w, 2, n, (int*)block_counts);
+  return (int)hipGetLastError();
+}
+
+// 64-bit sort + word1 gather + repair + segment count, all on the caller's
+// stream.  keys: (n,2) int64 rows 16 B apart.  Outputs: k0_sorted,
+// k1_sorted (n int64), perm32 (n uint32), block_counts (ceil(n/256) int32),
+// dirty_list and ctrl as in pw_gc_prefix_sort_count.  The odd-even passes
+// put right equal-word0 runs of up to passes+1 rows with distinct keys;
+// mark + repair on the whole of word0 (shift 0) then sort what they cannot:
+// longer runs and runs with repeated keys.  Overflow is left to the caller.
 extern "C" int pw_gc_sort_count(const void* keys, int64_t n, void* temp,
                                 int64_t temp_bytes, void* k0_sorted,
                                 void* k1_sorted, void* perm32, int passes,
+                                int64_t max_run, int64_t max_dirty,
+                                void* dirty_list, void* ctrl,
                                 void* block_counts, void* stream) {
   if (n < 2 || n >= ((int64_t)1 << 32)) return 1;
+  if (max_run < 2 || max_run > PW_GC_MAX_RUN_LIMIT) return 1;
+  if (max_dirty < 1 || max_dirty >= ((int64_t)1 << 32)) return 1;
   hipStream_t s = (hipStream_t)stream;
   size_t tb = (size_t)temp_bytes;
   hipError_t e = gc_sort(temp, tb, (const long long*)keys,
@@ -1863,20 +2067,54 @@ extern "C" int pw_gc_sort_count(const void* keys, int64_t n, void* temp,
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(k_gc_gather_k1, dim3(2 * PW_MAX_GRID), dim3(PW_BLOCK), 0,
                      s, (const long long*)keys, (const uint32_t*)perm32,
-                     (long long*)k1_sorted, n);
+                     (long long*)k1_sorted, n, (unsigned long long*)ctrl);
   int64_t pairs = n / 2 + 1;
   int64_t rblocks = (pairs + PW_BLOCK - 1) / PW_BLOCK;
   for (int p = 0; p < passes; ++p)
     hipLaunchKernelGGL(k_gc_sort_repair, dim3((uint32_t)rblocks),
                        dim3(PW_BLOCK), 0, s, (const long long*)k0_sorted,
                        (long long*)k1_sorted, (uint32_t*)perm32, n, p & 1);
-  SegWords w;
-  w.p[0] = (const int64_t*)k0_sorted;
-  w.p[1] = (const int64_t*)k1_sorted;
-  int64_t nblocks = (n + PW_BLOCK - 1) / PW_BLOCK;
-  hipLaunchKernelGGL(k_segred_count, dim3((uint32_t)nblocks), dim3(PW_BLOCK),
-                     0, s, w, 2, n, (int*)block_counts);
-  return (int)hipGetLastError();
+  return gc_repair_count(k0_sorted, k1_sorted, perm32, n, 0, max_run,
+                         max_dirty, dirty_list, ctrl, block_counts, s);
+}
+
+extern "C" int64_t pw_gc_temp_bytes_prefix(int64_t n) {
+  size_t bytes = 0;
+  if (n <= 0 || n >= ((int64_t)1 << 32)) return 0;
+  if (gc_sort_prefix(nullptr, bytes, nullptr, nullptr, nullptr, n, 32, 0) !=
+      hipSuccess)
+    return 0;
+  return (int64_t)bytes;
+}
+
+// prefix sort + gather + mark + repair + segment count, all on the caller's
+// stream.  Outputs as pw_gc_sort_count, plus dirty_list (max_dirty uint32)
+// and ctrl (2 uint64: overflow, listed runs).  k1_sorted doubles as the
+// scratch for the sorted prefixes until the gather overwrites it.
+extern "C" int pw_gc_prefix_sort_count(const void* keys, int64_t n, void* temp,
+                                       int64_t temp_bytes, void* k0_sorted,
+                                       void* k1_sorted, void* perm32,
+                                       int prefix_bits, int64_t max_run,
+                                       int64_t max_dirty, void* dirty_list,
+                                       void* ctrl, void* block_counts,
+                                       void* stream) {
+  if (n < 2 || n >= ((int64_t)1 << 32)) return 1;
+  if (prefix_bits < 1 || prefix_bits > 32) return 1;
+  if (max_run < 2 || max_run > PW_GC_MAX_RUN_LIMIT) return 1;
+  if (max_dirty < 1 || max_dirty >= ((int64_t)1 << 32)) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  size_t tb = (size_t)temp_bytes;
+  hipError_t e = gc_sort_prefix(temp, tb, (const long long*)keys,
+                                (uint32_t*)k1_sorted, (uint32_t*)perm32, n,
+                                prefix_bits, s);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(k_gc_gather_k01, dim3(2 * PW_MAX_GRID), dim3(PW_BLOCK), 0,
+                     s, (const long long*)keys, (const uint32_t*)perm32,
+                     (long long*)k0_sorted, (long long*)k1_sorted, n,
+                     (unsigned long long*)ctrl);
+  return gc_repair_count(k0_sorted, k1_sorted, perm32, n, 64 - prefix_bits,
+                         max_run, max_dirty, dirty_list, ctrl, block_counts,
+                         s);
 }
 
 extern "C" int pw_gc_emit(const void* k0_sorted, const void* k1_sorted,
