@@ -73,6 +73,15 @@ _PW_NO_GROUP_COMBINE = bool(_os.environ.get("PW_NO_GROUP_COMBINE"))
 _PW_HASHAGG = bool(_os.environ.get("PW_HASHAGG"))
 _PW_NO_HASHAGG = bool(_os.environ.get("PW_NO_HASHAGG"))
 
+#: group update (pw_group_update_*: merged state and emitted old/new rows
+#: from one merge walk) for count / int64 sum reduces — default ON;
+#: PW_NO_GROUP_UPDATE=1 forces the lookup / merge / lookup / compare chain
+#: (A/B)
+_PW_NO_GROUP_UPDATE = bool(_os.environ.get("PW_NO_GROUP_UPDATE"))
+
+#: returned by GroupReduceNode._group_update when the step is not its kind
+_NOT_FUSED = object()
+
 _node_counter = [0]
 
 
@@ -758,6 +767,12 @@ class GroupReduceNode(Node):
         elif ukeys_w is None:
             return None
 
+        # 4-7 in one native merge walk where the reduce is of that kind
+        if not has_multiset:
+            out = self._group_update(time, ukeys_w, acc_deltas, gcols_first, specs)
+            if out is not _NOT_FUSED:
+                return out
+
         # 4. affected keys + old output rows (pre-merge)
         changed = torch.stack(ukeys_w, dim=1)
         cw = ukeys_w
@@ -949,6 +964,115 @@ class GroupReduceNode(Node):
         self.add_accs = {name: acc.index_select(0, kidx) for name, acc in merged.items()}
         rep = perm2.index_select(0, first_idx).index_select(0, kidx)
         self.add_carried = {n: c.take(rep) for n, c in all_carried.items()}
+
+    def _group_update(self, time, ukeys_w, acc_deltas, gcols_first, specs):
+        """Steps 4-7 of `step` from one native merge walk
+        (ops.group_update_gpu): the walk that merges the consolidated
+        delta into the state knows, per delta key, the old and the new
+        accumulators, so it also writes the emitted rows.  Taken for
+        count / int64 sum reduces whose carried group columns are device
+        columns; returns _NOT_FUSED otherwise, with nothing changed."""
+        device = self.device
+        if (
+            torch.device(device).type != "cuda"
+            or _PW_NO_SEGRED
+            or _PW_NO_GROUP_UPDATE
+            or not ukeys_w[0].is_cuda
+        ):
+            return _NOT_FUSED
+        for spec, _args, _kwargs in specs.values():
+            if spec.family != "additive" or spec.name not in ("count", "sum"):
+                return _NOT_FUSED
+        fresh = self.add_keys is None
+        state_accs = acc_deltas if fresh else self.add_accs
+        names = sorted(state_accs, key=lambda nm: nm != "__w__")  # weight first
+        if not 1 <= len(names) <= 8 or names[0] != "__w__":
+            return _NOT_FUSED
+        for nm in names:
+            d = acc_deltas.get(nm)
+            if state_accs[nm].dtype != torch.int64 or (
+                d is not None and d.dtype != torch.int64
+            ):
+                return _NOT_FUSED
+        slots = {}
+        for out_name, (spec, _args, _kwargs) in specs.items():
+            if spec.name == "count":
+                slots[out_name] = 0
+            elif out_name in names:
+                slots[out_name] = names.index(out_name)
+            else:
+                return _NOT_FUSED
+        carried_names = list(gcols_first if fresh else self.add_carried)
+        if any(n not in carried_names for n in self.group_exprs):
+            return _NOT_FUSED
+        for n in carried_names:
+            c = gcols_first.get(n)
+            s = c if fresh else self.add_carried[n]
+            if type(c) is not type(s):
+                return _NOT_FUSED
+            if isinstance(c, TensorColumn):
+                # NaN != NaN would make the chain re-emit an unchanged row
+                if (
+                    c.tensor.dtype != s.tensor.dtype
+                    or c.tensor.dim() != 1
+                    or c.tensor.is_floating_point()
+                ):
+                    return _NOT_FUSED
+            elif isinstance(c, StringColumn):
+                if c.pool is not s.pool:
+                    return _NOT_FUSED
+            elif not isinstance(c, PointerColumn):
+                return _NOT_FUSED
+
+        from pathway_amd import ops
+
+        nseg = ukeys_w[0].shape[0]
+        z = torch.zeros((0,), dtype=torch.int64, device=device)
+        if fresh:
+            a_keys = [z, z]
+            a_accs = [z] * len(names)
+            idx0 = torch.zeros((0,), dtype=torch.int64)
+            a_carried = {
+                n: gcols_first[n].take(idx0.to(gcols_first[n]._device()))
+                for n in carried_names
+            }
+        else:
+            a_keys = self.add_keys
+            a_accs = [self.add_accs[nm] for nm in names]
+            a_carried = self.add_carried
+        b_accs = [
+            acc_deltas[nm]
+            if nm in acc_deltas
+            else torch.zeros(nseg, dtype=torch.int64, device=device)
+            for nm in names
+        ]
+        out_slots = sorted(set(slots.values()))
+        out_words, out_accs, rep, keys, diffs, vals, src = ops.group_update_gpu(
+            a_keys, a_accs, ukeys_w, b_accs, out_slots
+        )
+        all_carried = {
+            n: concat_columns([a_carried[n], gcols_first[n]]) for n in carried_names
+        }
+        self.add_keys = out_words
+        self.add_accs = dict(zip(names, out_accs))
+        self.add_carried = {n: c.take(rep) for n, c in all_carried.items()}
+        if keys.shape[0] == 0:
+            return None
+        cols: dict[str, Column] = {}
+        for name in self.group_exprs:
+            c = all_carried[name].take(src)
+            if isinstance(c, TensorColumn) and c.mask is None:
+                # the lookup chain attaches its found-mask to tensor columns
+                c = TensorColumn(
+                    c.tensor,
+                    c.dtype,
+                    torch.ones(len(c), dtype=torch.bool, device=c.tensor.device),
+                )
+            cols[name] = c
+        val_of = dict(zip(out_slots, vals))
+        for out_name, slot in slots.items():
+            cols[out_name] = TensorColumn(val_of[slot], dt.INT)
+        return DeltaBatch(keys, cols, diffs, time, consolidated=True)
 
     def _merge_multiset(self, gkeys, arg_cols, rowkeys, diffs, specs):
         ms_cols: dict[str, Column] = {}

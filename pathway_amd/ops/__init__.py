@@ -775,6 +775,111 @@ def merge_consolidate_gpu(
     return out_words, out_accs, rep
 
 
+def group_update_gpu(
+    a_words: Sequence[torch.Tensor],
+    a_accs: Sequence[torch.Tensor],
+    b_words: Sequence[torch.Tensor],
+    b_accs: Sequence[torch.Tensor],
+    out_slots: Sequence[int],
+):
+    """Merged state and emitted delta rows of a groupby-reduce step from
+    one merge walk (pw_group_update_*).
+
+    A (state) and B (consolidated delta) are unique lex-sorted 2-word row
+    sets with 1..8 int64 accumulators, slot 0 the weight.  The state half
+    is merge_consolidate_gpu's: (out_words, out_accs, rep).  The emitted
+    half holds, for every B row whose output row changes, a retraction of
+    the old row (old weight > 0) and an insertion of the new one (new
+    weight > 0); a row is unchanged when both weights are positive and no
+    slot of `out_slots` moves.  All retractions come first, then all
+    insertions, each in B order: keys (n_out, 2), diffs (-1 / +1), one
+    value tensor per slot of `out_slots` (in that order), and src, the
+    row of concat([A, B]) holding the key's carried values.
+
+    Returns (out_words, out_accs, rep, keys, diffs, vals, src).  One host
+    sync (the three output sizes).
+    """
+    lib = require_lib()
+    m = a_words[0].shape[0]
+    n = b_words[0].shape[0]
+    nacc = len(a_accs)
+    assert len(a_words) == 2 and len(b_words) == 2
+    assert len(b_accs) == nacc and 1 <= nacc <= 8
+    slots = sorted(set(int(s) for s in out_slots))
+    assert all(0 <= s < nacc for s in slots)
+    mask = 0
+    for s in slots:
+        mask |= 1 << s
+    device = b_words[0].device
+    nthreads = max(1, (m + n + 7) // 8)
+    counts = torch.empty(nthreads * 4, dtype=torch.int32, device=device)
+    bases = torch.empty(nthreads * 3, dtype=torch.int64, device=device)
+    totals = torch.empty(3, dtype=torch.int64, device=device)
+    wA = [t.contiguous() for t in a_words]
+    wB = [t.contiguous() for t in b_words]
+    aA = [t.contiguous() for t in a_accs]
+    aB = [t.contiguous() for t in b_accs]
+    for t in wA + wB + aA + aB:
+        assert t.dtype == torch.int64
+    rc = lib.pw_group_update_count(
+        _ptr_arr(wA),
+        _ptr_arr(aA),
+        _ptr_arr(wB),
+        _ptr_arr(aB),
+        ctypes.c_int(nacc),
+        ctypes.c_uint(mask),
+        ctypes.c_int64(m),
+        ctypes.c_int64(n),
+        ctypes.c_void_p(counts.data_ptr()),
+        ctypes.c_void_p(bases.data_ptr()),
+        ctypes.c_void_p(totals.data_ptr()),
+        ctypes.c_int64(nthreads),
+        _stream_ptr(),
+    )
+    if rc != 0:
+        raise RuntimeError(f"pw_group_update_count failed: {rc}")
+    n_keep, n_ret, n_ins = totals.tolist()  # the one host sync
+    n_out = n_ret + n_ins
+
+    def i64(k):
+        return torch.empty(k, dtype=torch.int64, device=device)
+
+    out_words = [i64(n_keep) for _ in range(2)]
+    out_accs = [i64(n_keep) for _ in range(nacc)]
+    rep = i64(n_keep)
+    keys = torch.empty((n_out, 2), dtype=torch.int64, device=device)
+    diffs = i64(n_out)
+    vals = {s: i64(n_out) for s in slots}
+    src = i64(n_out)
+    varr = (ctypes.c_void_p * 8)(
+        *[ctypes.c_void_p(vals[s].data_ptr() if s in vals else 0) for s in range(8)]
+    )
+    rc = lib.pw_group_update_emit(
+        _ptr_arr(wA),
+        _ptr_arr(aA),
+        _ptr_arr(wB),
+        _ptr_arr(aB),
+        ctypes.c_int(nacc),
+        ctypes.c_uint(mask),
+        ctypes.c_int64(m),
+        ctypes.c_int64(n),
+        ctypes.c_void_p(bases.data_ptr()),
+        ctypes.c_int64(n_ret),
+        ctypes.c_int64(nthreads),
+        _ptr_arr(out_words),
+        _ptr_arr(out_accs),
+        ctypes.c_void_p(rep.data_ptr()),
+        ctypes.c_void_p(keys.data_ptr()),
+        ctypes.c_void_p(diffs.data_ptr()),
+        varr,
+        ctypes.c_void_p(src.data_ptr()),
+        _stream_ptr(),
+    )
+    if rc != 0:
+        raise RuntimeError(f"pw_group_update_emit failed: {rc}")
+    return out_words, out_accs, rep, keys, diffs, [vals[s] for s in slots], src
+
+
 def radix_sort64_gpu(keys: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     """Hand-written LSD radix sort of int64 keys (signed order).
 

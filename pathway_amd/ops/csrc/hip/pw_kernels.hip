@@ -1303,6 +1303,301 @@ extern "C" int pw_merge_consolidate_emit(
   return (int)hipGetLastError();
 }
 
+// ------------------------------------------------------------ group update --
+// The groupby-reduce step on top of the merge above: the same walk over
+// unique-sorted state A and unique-sorted delta B (2-word keys) that
+// writes the merged state also writes the emitted delta batch, so the
+// two binary-search lookups (before and after the merge) and the
+// gather / mask / compare / nonzero / index_select / cat chain behind
+// them are not needed.  Every B row j is consumed by exactly one thread,
+// which has in registers
+//   old[c] = matched ? accA[c][ai] : 0        new[c] = old[c] + accB[c][j]
+//   old_p = old[0] > 0                        new_p = new[0] > 0
+//   unchanged = old_p && new_p && old[c] == new[c] for every exposed slot
+// and emits a retraction (old values, diff -1) when old_p && !unchanged
+// and an insertion (new values, diff +1) when new_p && !unchanged.  The
+// emitted rows are all retractions, then all insertions, each in B order.
+// src[] is the row of concat([A, B]) that holds the key's carried group
+// values (ai when matched, else m + j).
+//
+// count (3 counts per thread) -> single-block exclusive scan (bases and
+// the 3 totals) -> one host read of the totals -> emit.
+
+struct GuOut {
+  int64_t* words[2];   // new state keys
+  long long* accs[8];  // new state accumulators
+  int64_t* rep;        // new state row -> row of concat([A, B])
+  int64_t* keys;       // emitted keys, interleaved (n_out, 2)
+  int64_t* diffs;      // emitted diffs
+  long long* vals[8];  // emitted values, exposed slots only
+  int64_t* src;        // emitted row -> row of concat([A, B])
+};
+
+// per-thread counts / bases: kept state rows, retractions, insertions
+#define PW_GU_KEEP 0
+#define PW_GU_RET 1
+#define PW_GU_INS 2
+
+template <bool WRITE>
+__device__ __forceinline__ void gu_brow(McAcc accA, McWords B, McAcc accB,
+                                        int nacc, unsigned out_slots,
+                                        int64_t m, bool matched, int64_t ai,
+                                        int64_t bi, int* cnt, int64_t* w,
+                                        const GuOut& O) {
+  long long old0 = matched ? accA.p[0][ai] : 0ll;
+  long long new0 = old0 + accB.p[0][bi];
+  bool old_p = old0 > 0, new_p = new0 > 0;
+  // old[c] == new[c] exactly when the delta of slot c is zero
+  bool same = true;
+  for (int c = 0; c < nacc; ++c)
+    if (((out_slots >> c) & 1u) && accB.p[c][bi] != 0) same = false;
+  bool unchanged = old_p && new_p && same;
+  if (old_p && !unchanged) {  // old_p implies matched
+    if (WRITE) {
+      int64_t r = w[PW_GU_RET]++;
+      O.keys[2 * r] = B.p[0][bi];
+      O.keys[2 * r + 1] = B.p[1][bi];
+      O.diffs[r] = -1;
+      for (int c = 0; c < nacc; ++c)
+        if ((out_slots >> c) & 1u) O.vals[c][r] = accA.p[c][ai];
+      O.src[r] = ai;
+    }
+    ++cnt[PW_GU_RET];
+  }
+  if (new_p && !unchanged) {
+    if (WRITE) {
+      int64_t r = w[PW_GU_INS]++;
+      O.keys[2 * r] = B.p[0][bi];
+      O.keys[2 * r + 1] = B.p[1][bi];
+      O.diffs[r] = 1;
+      for (int c = 0; c < nacc; ++c)
+        if ((out_slots >> c) & 1u)
+          O.vals[c][r] = (matched ? accA.p[c][ai] : 0ll) + accB.p[c][bi];
+      O.src[r] = matched ? ai : m + bi;
+    }
+    ++cnt[PW_GU_INS];
+  }
+}
+
+// mc_walk with nw = nwc = 2 plus the per-B-row emission.  w[] holds the
+// three write cursors (WRITE only); cnt[] returns the three counts.
+template <bool WRITE>
+__device__ void gu_walk(McWords A, McAcc accA, McWords B, McAcc accB,
+                        int nacc, unsigned out_slots, int64_t m, int64_t n,
+                        int64_t d0, int64_t d1, int* cnt, int64_t* w,
+                        const GuOut& O) {
+  int64_t ai = mc_merge_path(A, m, B, n, d0, 2);
+  int64_t bi = d0 - ai;
+  int64_t d = d0;
+  // skip rule: a range starting on the B half of a match
+  if (d < d1 && bi < n && ai > 0 &&
+      !(ai < m && mc_le(A, ai, B, bi, 2))) {
+    if (mc_eq(A, ai - 1, B, bi, 2)) {
+      ++bi;
+      ++d;
+    }
+  }
+  while (d < d1) {
+    bool take_a = (bi >= n) || (ai < m && mc_le(A, ai, B, bi, 2));
+    if (take_a) {
+      bool matched = (bi < n) && mc_eq(A, ai, B, bi, 2);
+      long long wsum = accA.p[0][ai] + (matched ? accB.p[0][bi] : 0ll);
+      if (wsum != 0) {
+        if (WRITE) {
+          int64_t r = w[PW_GU_KEEP]++;
+          O.words[0][r] = A.p[0][ai];
+          O.words[1][r] = A.p[1][ai];
+          for (int c = 0; c < nacc; ++c)
+            O.accs[c][r] = accA.p[c][ai] + (matched ? accB.p[c][bi] : 0ll);
+          O.rep[r] = ai;
+        }
+        ++cnt[PW_GU_KEEP];
+      }
+      if (matched) {
+        gu_brow<WRITE>(accA, B, accB, nacc, out_slots, m, true, ai, bi, cnt,
+                       w, O);
+        ++bi;
+        ++d;
+      }
+      ++ai;
+      ++d;
+    } else {
+      long long wsum = accB.p[0][bi];
+      if (wsum != 0) {
+        if (WRITE) {
+          int64_t r = w[PW_GU_KEEP]++;
+          O.words[0][r] = B.p[0][bi];
+          O.words[1][r] = B.p[1][bi];
+          for (int c = 0; c < nacc; ++c) O.accs[c][r] = accB.p[c][bi];
+          O.rep[r] = m + bi;
+        }
+        ++cnt[PW_GU_KEEP];
+      }
+      gu_brow<WRITE>(accA, B, accB, nacc, out_slots, m, false, ai, bi, cnt, w,
+                     O);
+      ++bi;
+      ++d;
+    }
+  }
+}
+
+// thread_counts: (nthreads, 4) int32 — keep, retract, insert, pad
+__global__ void k_gu_count(McWords A, McAcc accA, McWords B, McAcc accB,
+                           int nacc, unsigned out_slots, int64_t m, int64_t n,
+                           int4* thread_counts, int64_t nthreads) {
+  int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nthreads) return;
+  int64_t d0 = t * PW_MC_CHUNK;
+  int64_t d1 = min(d0 + PW_MC_CHUNK, m + n);
+  int cnt[3] = {0, 0, 0};
+  GuOut none{};
+  gu_walk<false>(A, accA, B, accB, nacc, out_slots, m, n, d0, d1, cnt,
+                 nullptr, none);
+  thread_counts[t] = make_int4(cnt[0], cnt[1], cnt[2], 0);
+}
+
+// Exclusive scan of the three per-thread counts in one block: tiles of
+// THREADS * ITEMS threads' counts, int32 inside a tile (a thread counts at
+// most PW_MC_CHUNK rows of each kind), int64 carry across tiles.
+// bases: (nthreads, 3) int64; totals: 3 int64.
+#define PW_GU_SCAN_THREADS 1024
+#define PW_GU_SCAN_ITEMS 4
+
+__global__ __launch_bounds__(PW_GU_SCAN_THREADS) void k_gu_scan(
+    const int4* thread_counts, int64_t nthreads, int64_t* bases,
+    int64_t* totals) {
+  __shared__ int wave_tot[PW_GU_SCAN_THREADS / 64][3];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  long long carry[3] = {0, 0, 0};
+  const int64_t tile = (int64_t)PW_GU_SCAN_THREADS * PW_GU_SCAN_ITEMS;
+  for (int64_t t0 = 0; t0 < nthreads; t0 += tile) {
+    int64_t first = t0 + (int64_t)tid * PW_GU_SCAN_ITEMS;
+    int v[PW_GU_SCAN_ITEMS][3];
+    int sum[3] = {0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < PW_GU_SCAN_ITEMS; ++k) {
+      int4 c = make_int4(0, 0, 0, 0);
+      if (first + k < nthreads) c = thread_counts[first + k];
+      v[k][0] = c.x;
+      v[k][1] = c.y;
+      v[k][2] = c.z;
+      sum[0] += c.x;
+      sum[1] += c.y;
+      sum[2] += c.z;
+    }
+    int incl[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      int x = sum[a];
+      for (int dlt = 1; dlt < 64; dlt <<= 1) {
+        int y = __shfl_up(x, dlt, 64);
+        if (lane >= dlt) x += y;
+      }
+      incl[a] = x;
+      if (lane == 63) wave_tot[wave][a] = x;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      int before = 0, all = 0;
+      for (int wv = 0; wv < PW_GU_SCAN_THREADS / 64; ++wv) {
+        int wt = wave_tot[wv][a];
+        if (wv < wave) before += wt;
+        all += wt;
+      }
+      long long run = carry[a] + before + incl[a] - sum[a];
+#pragma unroll
+      for (int k = 0; k < PW_GU_SCAN_ITEMS; ++k) {
+        if (first + k < nthreads) bases[(first + k) * 3 + a] = run;
+        run += v[k][a];
+      }
+      carry[a] += all;
+    }
+    __syncthreads();
+  }
+  if (tid < 3) totals[tid] = carry[tid];
+}
+
+__global__ void k_gu_emit(McWords A, McAcc accA, McWords B, McAcc accB,
+                          int nacc, unsigned out_slots, int64_t m, int64_t n,
+                          const int64_t* bases, int64_t n_ret,
+                          int64_t nthreads, GuOut O) {
+  int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nthreads) return;
+  int64_t d0 = t * PW_MC_CHUNK;
+  int64_t d1 = min(d0 + PW_MC_CHUNK, m + n);
+  int cnt[3] = {0, 0, 0};
+  int64_t w[3] = {bases[t * 3 + PW_GU_KEEP], bases[t * 3 + PW_GU_RET],
+                  n_ret + bases[t * 3 + PW_GU_INS]};
+  gu_walk<true>(A, accA, B, accB, nacc, out_slots, m, n, d0, d1, cnt, w, O);
+}
+
+static void gu_args(const void** wordsA, const void** accA,
+                    const void** wordsB, const void** accB, int nacc,
+                    McWords* WA, McAcc* A, McWords* WB, McAcc* B) {
+  for (int c = 0; c < nacc; ++c) {
+    A->p[c] = (const long long*)accA[c];
+    B->p[c] = (const long long*)accB[c];
+  }
+  for (int k = 0; k < 2; ++k) {
+    WA->p[k] = (const int64_t*)wordsA[k];
+    WB->p[k] = (const int64_t*)wordsB[k];
+  }
+}
+
+// count + scan: thread_counts (nthreads, 4) int32 scratch, bases
+// (nthreads, 3) int64, totals 3 int64 (state rows, retractions, insertions)
+extern "C" int pw_group_update_count(
+    const void** wordsA, const void** accA, const void** wordsB,
+    const void** accB, int nacc, unsigned out_slots, int64_t m, int64_t n,
+    void* thread_counts, void* bases, void* totals, int64_t nthreads,
+    void* stream) {
+  if (nacc > 8 || nacc < 1 || nthreads < 1) return 2;
+  McAcc A{}, B{};
+  McWords WA{}, WB{};
+  gu_args(wordsA, accA, wordsB, accB, nacc, &WA, &A, &WB, &B);
+  hipStream_t s = (hipStream_t)stream;
+  int64_t blocks = (nthreads + PW_BLOCK - 1) / PW_BLOCK;
+  hipLaunchKernelGGL(k_gu_count, dim3((uint32_t)blocks), dim3(PW_BLOCK), 0, s,
+                     WA, A, WB, B, nacc, out_slots, m, n,
+                     (int4*)thread_counts, nthreads);
+  hipLaunchKernelGGL(k_gu_scan, dim3(1), dim3(PW_GU_SCAN_THREADS), 0, s,
+                     (const int4*)thread_counts, nthreads, (int64_t*)bases,
+                     (int64_t*)totals);
+  return (int)hipGetLastError();
+}
+
+// out_vals[c] is read for the slots of out_slots only
+extern "C" int pw_group_update_emit(
+    const void** wordsA, const void** accA, const void** wordsB,
+    const void** accB, int nacc, unsigned out_slots, int64_t m, int64_t n,
+    const void* bases, int64_t n_ret, int64_t nthreads, void** out_words,
+    void** out_accs, void* rep, void* out_keys, void* out_diffs,
+    void** out_vals, void* src, void* stream) {
+  if (nacc > 8 || nacc < 1 || nthreads < 1) return 2;
+  McAcc A{}, B{};
+  McWords WA{}, WB{};
+  gu_args(wordsA, accA, wordsB, accB, nacc, &WA, &A, &WB, &B);
+  GuOut O{};
+  for (int k = 0; k < 2; ++k) O.words[k] = (int64_t*)out_words[k];
+  for (int c = 0; c < nacc; ++c) {
+    O.accs[c] = (long long*)out_accs[c];
+    if ((out_slots >> c) & 1u) O.vals[c] = (long long*)out_vals[c];
+  }
+  O.rep = (int64_t*)rep;
+  O.keys = (int64_t*)out_keys;
+  O.diffs = (int64_t*)out_diffs;
+  O.src = (int64_t*)src;
+  hipStream_t s = (hipStream_t)stream;
+  int64_t blocks = (nthreads + PW_BLOCK - 1) / PW_BLOCK;
+  hipLaunchKernelGGL(k_gu_emit, dim3((uint32_t)blocks), dim3(PW_BLOCK), 0, s,
+                     WA, A, WB, B, nacc, out_slots, m, n,
+                     (const int64_t*)bases, n_ret, nthreads, O);
+  return (int)hipGetLastError();
+}
+
 // -------------------------------------------------------------- radix sort --
 // Hand-written LSD radix sort of int64 keys with an int64 payload (the
 // permutation) — the mandated sort kernel for the 128-bit key path

@@ -303,3 +303,6 @@ class PersistenceManager:
     def close(self):
         for w in self.writers.values():
             w.close()
+        # the last operator snapshot is written on a background thread: a
+        # reader that opens the store after close() must find it complete
+        self.op_store.wait()
