@@ -3,6 +3,11 @@
 Environment variables:
   PATHWAY_THREADS / PATHWAY_PROCESSES — worker counts (reference semantics)
   PW_DEVICE — engine device override ("cpu", "cuda", "cuda:0", ...)
+  PW_BM25 — BM25 index state override for A/B runs: "host" (numpy CSR,
+    float64, one query at a time) or "device" (CSR postings on the node's
+    device, batched pw_bm25_score kernel, float32).  Unset: device on a
+    GPU node, host on a CPU node.  Read when the index node is built
+    (stdlib/indexing/bm25.py).
 On GPU hosts the engine defaults to cuda (one worker per GPU, RCCL
 exchange); in CPU-only containers it runs on torch-cpu tensors.
 """

@@ -693,6 +693,85 @@ def topk_gpu(scores: torch.Tensor, k: int) -> tuple[torch.Tensor, torch.Tensor]:
     return vals, idx
 
 
+#: doc slots per block of pw_bm25_score (PW_BM25_TILE in pw_kernels.hip);
+#: tests size their corpora around it
+BM25_TILE = 4096
+
+
+def bm25_score(
+    offsets: torch.Tensor,
+    pidx: torch.Tensor,
+    ptf: torch.Tensor,
+    norm: torch.Tensor,
+    q_off: torch.Tensor,
+    q_term: torch.Tensor,
+    q_idf: torch.Tensor,
+    k1: float,
+    pad_to: int = 1,
+) -> torch.Tensor:
+    """Okapi BM25 scores of a query batch over compiled CSR postings.
+
+    offsets (V+1) int64, pidx (nnz) int32 doc slots ascending within each
+    term, ptf (nnz) float32, norm (n) float32 = k1*(1-b+b*dl/avgdl); the
+    batch in CSR form: q_off (Q+1) int32, q_term int32 (distinct term ids
+    < V), q_idf float32.  Returns dense float32 scores (Q, n), where
+    scores[q, d] = sum over q's terms of idf * tf*(k1+1) / (tf + norm[d]),
+    summed in term order.  With pad_to > 1 the rows are padded with zeros
+    to the next multiple of pad_to columns, so that a row splits into
+    equal contiguous segments.
+
+    CUDA tensors go through the pw_bm25_score kernel; CPU tensors run the
+    same formula in torch (one float32 index_add_ per term), which is the
+    CPU path and a second numerics reference for the kernel.
+    """
+    n = norm.shape[0]
+    nq = q_off.shape[0] - 1
+    assert offsets.dtype == torch.int64 and pidx.dtype == torch.int32
+    assert ptf.dtype == torch.float32 and norm.dtype == torch.float32
+    assert q_off.dtype == torch.int32 and q_term.dtype == torch.int32
+    assert q_idf.dtype == torch.float32
+    assert pidx.shape == ptf.shape and q_term.shape == q_idf.shape
+    assert nq >= 0 and offsets.shape[0] >= 1
+    k1p1 = float(k1) + 1.0
+    n_pad = -(-n // pad_to) * pad_to
+    if not norm.is_cuda:
+        scores = torch.zeros((nq, n_pad), dtype=torch.float32)
+        k1p1_t = torch.tensor(k1p1, dtype=torch.float32)
+        qo = q_off.tolist()
+        for q in range(nq):
+            row = scores[q]
+            for t in range(qo[q], qo[q + 1]):
+                term = int(q_term[t])
+                s, e = int(offsets[term]), int(offsets[term + 1])
+                d = pidx[s:e].long()
+                tf = ptf[s:e]
+                row.index_add_(0, d, q_idf[t] * (tf * k1p1_t) / (tf + norm[d]))
+        return scores
+    lib = require_lib()
+    assert BM25_TILE == lib.pw_bm25_tile(), "BM25_TILE out of step with the kernel"
+    scores = torch.empty((nq, n_pad), dtype=torch.float32, device=norm.device)
+    if n_pad > n:
+        scores[:, n:] = 0.0
+    rc = lib.pw_bm25_score(
+        ctypes.c_void_p(offsets.contiguous().data_ptr()),
+        ctypes.c_void_p(pidx.contiguous().data_ptr()),
+        ctypes.c_void_p(ptf.contiguous().data_ptr()),
+        ctypes.c_void_p(norm.contiguous().data_ptr()),
+        ctypes.c_int64(n),
+        ctypes.c_void_p(q_off.contiguous().data_ptr()),
+        ctypes.c_void_p(q_term.contiguous().data_ptr()),
+        ctypes.c_void_p(q_idf.contiguous().data_ptr()),
+        ctypes.c_int64(nq),
+        ctypes.c_float(k1p1),
+        ctypes.c_void_p(scores.data_ptr()),
+        ctypes.c_int64(n_pad),
+        _stream_ptr(),
+    )
+    if rc != 0:
+        raise RuntimeError(f"pw_bm25_score failed: hip error {rc}")
+    return scores
+
+
 def merge_consolidate_gpu(
     a_words: Sequence[torch.Tensor],
     a_accs: Sequence[torch.Tensor],

@@ -1106,6 +1106,95 @@ extern "C" int pw_topk(const void* scores, int64_t nq, int64_t m, int k,
   return (int)hipGetLastError();
 }
 
+// ------------------------------------------------------------ BM25 score --
+// Okapi BM25 over compiled CSR postings for a batch of queries: dense
+// scores (nq, n) in rows of row_stride >= n floats, every one of the n
+// elements of a row written (the pad beyond n is the caller's).  offsets
+// (V+1) int64, pidx (nnz) int32 doc slots ASCENDING WITHIN EACH TERM, ptf
+// (nnz) term frequencies, norm (n) = k1*(1-b+b*dl/avgdl).  The query
+// batch is CSR too: q_off (nq+1) int32 into q_term (distinct known term
+// ids, < V) and q_idf.
+//
+// Grid (ceil(n/TILE), nq).  A block owns TILE consecutive doc slots and
+// keeps their accumulators in LDS (16 KiB).  Per term it binary-searches
+// the sub-range of the term's postings that falls in its tile, and its
+// threads stride over that sub-range.  Doc slots are unique within a
+// term, so no two lanes add to one accumulator; a barrier separates the
+// terms (the term count is per query, hence block-uniform).  No float
+// atomics: each accumulator is summed by one thread per term, in term
+// order, so the result is bitwise reproducible.  A block reads at most
+// TILE postings per term whatever the term's document frequency.
+
+#define PW_BM25_TILE 4096
+#define PW_BM25_MAX_GRID_Y 65535
+
+// first p in [lo, hi) with a[p] >= x (hi if none)
+__device__ __forceinline__ int64_t bm25_lower_bound(
+    const int* __restrict__ a, int64_t lo, int64_t hi, int x) {
+  while (lo < hi) {
+    int64_t mid = lo + ((hi - lo) >> 1);
+    if (a[mid] < x) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+__global__ __launch_bounds__(256) void k_bm25_score(
+    const int64_t* __restrict__ offsets, const int* __restrict__ pidx,
+    const float* __restrict__ ptf, const float* __restrict__ norm,
+    const int* __restrict__ q_off, const int* __restrict__ q_term,
+    const float* __restrict__ q_idf, float k1p1, int n, int64_t row_stride,
+    float* __restrict__ scores) {
+  __shared__ float acc[PW_BM25_TILE];
+  const int tid = threadIdx.x;
+  const int q = blockIdx.y;
+  const int tile_lo = blockIdx.x * PW_BM25_TILE;  // < n < 2^31
+  const int tile_n = min(PW_BM25_TILE, n - tile_lo);
+  for (int i = tid; i < PW_BM25_TILE; i += 256) acc[i] = 0.0f;
+  __syncthreads();
+  const int t_end = q_off[q + 1];
+  for (int t = q_off[q]; t < t_end; ++t) {
+    const int term = q_term[t];
+    const float idf = q_idf[t];
+    const int64_t e = offsets[term + 1];
+    const int64_t lo = bm25_lower_bound(pidx, offsets[term], e, tile_lo);
+    // tile_lo + tile_n <= n fits an int
+    const int64_t hi = bm25_lower_bound(pidx, lo, e, tile_lo + tile_n);
+    for (int64_t p = lo + tid; p < hi; p += 256) {
+      const int d = pidx[p];  // in [tile_lo, tile_lo + tile_n)
+      const float tf = ptf[p];
+      acc[d - tile_lo] += idf * (tf * k1p1) / (tf + norm[d]);
+    }
+    __syncthreads();
+  }
+  float* row = scores + (int64_t)q * row_stride + tile_lo;
+  for (int i = tid; i < tile_n; i += 256) row[i] = acc[i];
+}
+
+extern "C" int pw_bm25_tile() { return PW_BM25_TILE; }
+
+extern "C" int pw_bm25_score(const void* offsets, const void* pidx,
+                             const void* ptf, const void* norm, int64_t n,
+                             const void* q_off, const void* q_term,
+                             const void* q_idf, int64_t nq, float k1p1,
+                             void* scores, int64_t row_stride,
+                             void* stream) {
+  if (n < 0 || n >= ((int64_t)1 << 31) || nq < 0 || row_stride < n) return 2;
+  if (n == 0 || nq == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  uint32_t tiles = (uint32_t)((n + PW_BM25_TILE - 1) / PW_BM25_TILE);
+  for (int64_t q0 = 0; q0 < nq; q0 += PW_BM25_MAX_GRID_Y) {
+    int64_t qc = nq - q0 < PW_BM25_MAX_GRID_Y ? nq - q0 : PW_BM25_MAX_GRID_Y;
+    hipLaunchKernelGGL(k_bm25_score, dim3(tiles, (uint32_t)qc), dim3(256), 0,
+                       s, (const int64_t*)offsets, (const int*)pidx,
+                       (const float*)ptf, (const float*)norm,
+                       (const int*)q_off + q0, (const int*)q_term,
+                       (const float*)q_idf, k1p1, (int)n, row_stride,
+                       (float*)scores + q0 * row_stride);
+  }
+  return (int)hipGetLastError();
+}
+
 // --------------------------------------------------- merge-consolidate --
 // Fused LSM merge of the additive-reduce state:
 // two UNIQUE lex-sorted 128-bit-key row sets (state A, delta B) with
