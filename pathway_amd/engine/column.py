@@ -54,11 +54,35 @@ class StringPool:
         # True when every worker is known to hold an identical pool (codes
         # agree across ranks) — lets the exchange ship codes instead of bytes
         self.synchronized = False
+        # attached device dictionaries (engine/device_dict.py) by device:
+        # they may hold tokens interned on the device that this host pool
+        # has not seen yet; everything that reads or grows _strs drains
+        # them first, so host- and device-assigned codes never collide
+        self._dicts: dict[str, Any] = {}
+
+    def device_dictionary(self, device):
+        """The pool's DeviceDictionary on `device` (one per device)."""
+        from pathway_amd.engine.device_dict import DeviceDictionary, device_key
+
+        key = device_key(device)
+        d = self._dicts.get(key)
+        if d is None:
+            d = DeviceDictionary(self, device)
+            self._dicts[key] = d
+        return d
+
+    def _drain(self) -> None:
+        for d in self._dicts.values():
+            d.sync_host()
 
     def __len__(self) -> int:
+        if self._dicts:
+            self._drain()
         return len(self._strs)
 
-    def code(self, s: str) -> int:
+    def _intern_host(self, s: str) -> int:
+        """code() without the drain — also what a draining dictionary
+        appends its tokens with."""
         c = self._index.get(s)
         if c is None:
             c = len(self._strs)
@@ -69,7 +93,14 @@ class StringPool:
             self._hash_hi.append(_signed(hi))
         return c
 
+    def code(self, s: str) -> int:
+        if self._dicts:
+            self._drain()
+        return self._intern_host(s)
+
     def codes(self, values: Sequence[str]) -> np.ndarray:
+        if self._dicts:
+            self._drain()
         idx = self._index
         out = np.empty(len(values), dtype=np.int64)
         for i, v in enumerate(values):
@@ -78,18 +109,32 @@ class StringPool:
             else:
                 c = idx.get(v)
                 if c is None:
-                    c = self.code(v)
+                    c = self._intern_host(v)
                 out[i] = c
         return out
 
     def value(self, code: int) -> str | None:
-        return None if code < 0 else self._strs[code]
+        if code < 0:
+            return None
+        if self._dicts and code >= len(self._strs):
+            self._drain()
+        return self._strs[code]
 
     def extend_from(self, strings: Sequence[str]) -> np.ndarray:
         return self.codes(strings)
 
     def hash_tensors(self, device) -> tuple[torch.Tensor, torch.Tensor]:
-        """(pool_size,) int64 lo/hi hash tensors on `device`, cached."""
+        """int64 lo/hi hash tensors on `device`, row index == code.  With
+        a dictionary attached on `device` they are views of its device
+        arrays (covering every code interned there, no host round trip);
+        otherwise (pool_size,) tensors built from the host lists, cached."""
+        if self._dicts:
+            from pathway_amd.engine.device_dict import device_key
+
+            d = self._dicts.get(device_key(device))
+            if d is not None and d.native:
+                return d.hash_tensors()
+            self._drain()
         key = str(device)
         cached = self._device_hashes.get(key)
         n = len(self._strs)

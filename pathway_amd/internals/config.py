@@ -8,6 +8,14 @@ Environment variables:
     device, batched pw_bm25_score kernel, float32).  Unset: device on a
     GPU node, host on a CPU node.  Read when the index node is built
     (stdlib/indexing/bm25.py).
+  PW_INGEST — pw.io.plaintext.read path override: "host" (python lines
+    through StringPool.codes) or "device" (file bytes to the device,
+    newline scan, unseen lines interned there by the pool's
+    DeviceDictionary; on a CPU node its numpy fallback).  Unset: device on
+    a GPU node with the native library, host otherwise.  A read with a
+    file that holds a carriage return or invalid UTF-8 takes the host path
+    as a whole, so its rows and exceptions stay what they were.  Read when
+    the reader is built (engine/ingest_device.py).
 On GPU hosts the engine defaults to cuda (one worker per GPU, RCCL
 exchange); in CPU-only containers it runs on torch-cpu tensors.
 """

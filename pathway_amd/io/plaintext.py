@@ -12,6 +12,14 @@ def read(path: str, *, mode: str = "streaming", name: str | None = None, **kwarg
     from pathway_amd.io._utils import expand_paths
 
     files = expand_paths(path)
+    from pathway_amd.engine import ingest_device
+    from pathway_amd.internals.config import get_device
+
+    device = get_device()
+    if ingest_device.use_device_ingest(device):
+        table = ingest_device.read_plaintext(files, device)
+        if table is not None:
+            return table
     rows = []
     for f in files:
         with open(f) as fh:

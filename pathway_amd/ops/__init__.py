@@ -1131,35 +1131,206 @@ def gather_cols_gpu(idx: torch.Tensor, cols: list) -> list:
     return outs
 
 
+def intern_error_message(e: int) -> str:
+    """Text for the PW_HT_ERR_* bits of pw_kernels.hip."""
+    parts = []
+    if e & 1:
+        parts.append("probe bound hit (table full)")
+    if e & 2:
+        parts.append("slot, claimer row or span out of range")
+    if e & 4:
+        parts.append("dictionary arrays or byte arena too small")
+    return "device dictionary intern failed: " + "; ".join(parts or [str(e)])
+
+
+def gather_spans_gpu(
+    buf: torch.Tensor,
+    starts: torch.Tensor,
+    ends: torch.Tensor,
+    first_rows: torch.Tensor,
+    n_new: torch.Tensor,
+    base: torch.Tensor,
+    arena: torch.Tensor,
+    cursor: torch.Tensor,
+    tok_off: torch.Tensor,
+    tok_len: torch.Tensor,
+    err: torch.Tensor,
+) -> None:
+    """Pack the spans [starts[r], ends[r]) of rows r = first_rows[:n_new]
+    of the uint8 `buf` into `arena` (k_gather_spans) and record each
+    token's (offset, length) at code base+k.  n_new, base, cursor and err
+    are 1-element int64 device tensors; nothing waits for the device."""
+    lib = require_lib()
+    nrows = starts.shape[0]
+    if nrows == 0:
+        return
+    for t in (buf, starts, ends, first_rows, arena, tok_off, tok_len):
+        assert t.is_contiguous()
+    rc = lib.pw_gather_spans(
+        ctypes.c_void_p(buf.data_ptr()),
+        ctypes.c_int64(buf.shape[0]),
+        ctypes.c_void_p(starts.data_ptr()),
+        ctypes.c_void_p(ends.data_ptr()),
+        ctypes.c_int64(nrows),
+        ctypes.c_void_p(first_rows.data_ptr()),
+        ctypes.c_void_p(n_new.data_ptr()),
+        ctypes.c_void_p(base.data_ptr()),
+        ctypes.c_void_p(arena.data_ptr()),
+        ctypes.c_int64(arena.shape[0]),
+        ctypes.c_void_p(cursor.data_ptr()),
+        ctypes.c_void_p(tok_off.data_ptr()),
+        ctypes.c_void_p(tok_len.data_ptr()),
+        ctypes.c_int64(min(tok_off.shape[0], tok_len.shape[0])),
+        ctypes.c_void_p(err.data_ptr()),
+        _stream_ptr(),
+    )
+    if rc != 0:
+        raise RuntimeError(f"pw_gather_spans failed: hip error {rc}")
+
+
 class DeviceHashTable:
     """Open-addressing device hash table over 128-bit keys -> int64 values
-    (k_ht_build / k_ht_probe).  Build once per dictionary version; probe
-    per delta batch.  Load factor <= 0.5 (nslots = next pow2 >= 2m)."""
+    (k_ht_build / k_ht_probe / k_ht_intern_*).  Build from a dictionary's
+    hash arrays; probe per delta batch (closed world) or intern per delta
+    batch (unseen keys are inserted).  Load factor <= 0.5 (nslots = next
+    pow2 >= 2m)."""
 
     def __init__(self, klo: torch.Tensor, khi: torch.Tensor,
-                 vals: torch.Tensor | None = None):
-        lib = require_lib()
+                 vals: torch.Tensor | None = None, reserve: int = 0):
+        require_lib()
         m = klo.shape[0]
         device = klo.device
-        nslots = 1 << max(4, (2 * m - 1).bit_length()) if m else 16
-        self.nslots = nslots
+        self.nslots = self.slots_for(max(m, int(reserve)))
+        #: OR of the PW_HT_ERR_* bits raised by the intern kernels (int64,
+        #: 1 element; an owner may point it at a word of its own state)
+        self.err = torch.zeros(1, dtype=torch.int64, device=device)
+        self._alloc(device)
+        self.insert(klo, khi, vals)
+
+    @staticmethod
+    def slots_for(m: int) -> int:
+        """Smallest power-of-two slot count with load factor <= 0.5."""
+        return 1 << max(4, (2 * m - 1).bit_length()) if m else 16
+
+    def _alloc(self, device) -> None:
+        nslots = self.nslots
         self.tab_lo = torch.empty(nslots, dtype=torch.int64, device=device)
         self.tab_hi = torch.empty(nslots, dtype=torch.int64, device=device)
         self.tab_val = torch.full((nslots,), -1, dtype=torch.int64, device=device)
-        if m:
-            rc = lib.pw_ht_build(
-                ctypes.c_void_p(klo.contiguous().data_ptr()),
-                ctypes.c_void_p(khi.contiguous().data_ptr()),
-                ctypes.c_void_p(vals.contiguous().data_ptr()) if vals is not None else None,
-                ctypes.c_int64(m),
-                ctypes.c_void_p(self.tab_lo.data_ptr()),
-                ctypes.c_void_p(self.tab_hi.data_ptr()),
-                ctypes.c_void_p(self.tab_val.data_ptr()),
-                ctypes.c_int64(nslots),
-                _stream_ptr(),
-            )
-            if rc != 0:
-                raise RuntimeError(f"pw_ht_build failed: hip error {rc}")
+
+    def insert(self, klo: torch.Tensor, khi: torch.Tensor,
+               vals: torch.Tensor | None = None) -> None:
+        """pw_ht_build into the (possibly non-empty) table.  Keys must be
+        unique and absent; the caller keeps the load factor <= 0.5."""
+        lib = require_lib()
+        m = klo.shape[0]
+        if not m:
+            return
+        klo, khi = klo.contiguous(), khi.contiguous()
+        vals = vals.contiguous() if vals is not None else None
+        rc = lib.pw_ht_build(
+            ctypes.c_void_p(klo.data_ptr()),
+            ctypes.c_void_p(khi.data_ptr()),
+            ctypes.c_void_p(vals.data_ptr()) if vals is not None else None,
+            ctypes.c_int64(m),
+            ctypes.c_void_p(self.tab_lo.data_ptr()),
+            ctypes.c_void_p(self.tab_hi.data_ptr()),
+            ctypes.c_void_p(self.tab_val.data_ptr()),
+            ctypes.c_int64(self.nslots),
+            _stream_ptr(),
+        )
+        if rc != 0:
+            raise RuntimeError(f"pw_ht_build failed: hip error {rc}")
+
+    def fits(self, size: int) -> bool:
+        """True when `size` keys keep the load factor <= 0.5 — the bound
+        the intern kernels' probe loops rely on."""
+        return 2 * int(size) <= self.nslots
+
+    def rebuild(self, size: int, klo: torch.Tensor, khi: torch.Tensor) -> None:
+        """Re-hash into a table sized for `size` keys from the dictionary's
+        hash arrays (row index == code)."""
+        self.nslots = self.slots_for(max(int(size), klo.shape[0]))
+        self._alloc(klo.device)
+        self.insert(klo, khi, None)
+
+    def intern(
+        self,
+        qlo: torch.Tensor,
+        qhi: torch.Tensor,
+        base,
+        pool_lo: torch.Tensor,
+        pool_hi: torch.Tensor,
+        front: "DeviceHashTable | None" = None,
+    ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Insert-or-get (k_ht_intern_*): returns (codes, first_rows, n_new).
+
+        Known keys get their stored code; the batch's distinct new keys get
+        base, base+1, ... in order of first occurrence by row index, are
+        inserted, and their hashes written to pool_lo/pool_hi[base + k].
+        `base` is the current dictionary size, an int or a 1-element int64
+        device tensor (so a caller need not read it back).  first_rows[k]
+        (k < n_new) is the row that introduced code base+k; n_new is a
+        1-element device tensor — nothing here waits for the device.  The
+        caller guarantees fits(size + n) and pool capacity >= size + n;
+        violations raise bits in self.err instead of running out of bounds.
+
+        `front` is an optional second table holding keys this one does not
+        (a compact, cache-resident table of the keys known for certain):
+        it is probed first and never written, and only its misses reach
+        this table, which must be sized for a whole batch of new keys.
+        """
+        lib = require_lib()
+        n = qlo.shape[0]
+        device = qlo.device
+        codes = torch.empty(n, dtype=torch.int64, device=device)
+        first_rows = torch.empty(n, dtype=torch.int64, device=device)
+        if n == 0:
+            return codes, first_rows, torch.zeros(1, dtype=torch.int64, device=device)
+        if not torch.is_tensor(base):
+            base = torch.tensor([int(base)], dtype=torch.int64, device=device)
+        assert base.dtype == torch.int64 and base.is_contiguous()
+        assert pool_lo.is_contiguous() and pool_hi.is_contiguous()
+        qlo, qhi = qlo.contiguous(), qhi.contiguous()
+        # block counts and n_new share one allocation
+        nblocks = max(1, min(2048, (n + 4095) // 4096))
+        work = torch.empty(nblocks + 1, dtype=torch.int64, device=device)
+        pend = torch.empty(n, dtype=torch.uint8, device=device)
+        n_new = work[nblocks:]
+        rc = lib.pw_ht_intern(
+            ctypes.c_void_p(qlo.data_ptr()),
+            ctypes.c_void_p(qhi.data_ptr()),
+            ctypes.c_int64(n),
+            ctypes.c_void_p(self.tab_lo.data_ptr()),
+            ctypes.c_void_p(self.tab_hi.data_ptr()),
+            ctypes.c_void_p(self.tab_val.data_ptr()),
+            ctypes.c_int64(self.nslots),
+            ctypes.c_void_p(front.tab_lo.data_ptr() if front else None),
+            ctypes.c_void_p(front.tab_hi.data_ptr() if front else None),
+            ctypes.c_void_p(front.tab_val.data_ptr() if front else None),
+            ctypes.c_int64(front.nslots if front else 0),
+            ctypes.c_void_p(base.data_ptr()),
+            ctypes.c_void_p(pool_lo.data_ptr()),
+            ctypes.c_void_p(pool_hi.data_ptr()),
+            ctypes.c_int64(min(pool_lo.shape[0], pool_hi.shape[0])),
+            ctypes.c_void_p(codes.data_ptr()),
+            ctypes.c_void_p(pend.data_ptr()),
+            ctypes.c_void_p(first_rows.data_ptr()),
+            ctypes.c_void_p(work.data_ptr()),
+            ctypes.c_int64(nblocks),
+            ctypes.c_void_p(n_new.data_ptr()),
+            ctypes.c_void_p(self.err.data_ptr()),
+            _stream_ptr(),
+        )
+        if rc != 0:
+            raise RuntimeError(f"pw_ht_intern failed: hip error {rc}")
+        return codes, first_rows, n_new
+
+    def check_error(self) -> None:
+        """Blocking read of the intern kernels' error word."""
+        e = int(self.err.item())
+        if e:
+            raise RuntimeError(intern_error_message(e))
 
     def probe(self, qlo: torch.Tensor, qhi: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
         """Returns (values, found); values are -1 where not found."""

@@ -2085,6 +2085,391 @@ extern "C" int pw_ht_probe(const void* qlo, const void* qhi, int64_t nq,
   return (int)hipGetLastError();
 }
 
+// ------------------------------------------------- hash table: intern --
+// Insert-or-get on the same table (layout unchanged, -1 still empty):
+// known keys return their stored code, the batch's distinct new keys get
+// codes base, base+1, ... in order of first occurrence by row index —
+// what StringPool.codes() assigns on the host.  Four launches, lock-free,
+// no lane ever waits on a value another lane is expected to write:
+//
+//   claim    row i linear-probes.  A slot with val >= 0 is compared by
+//            tab_lo/tab_hi (written by an earlier launch).  A slot with
+//            val <= -2 is pending: it encodes its claimer row r as -(r+2)
+//            and is compared against qlo[r]/qhi[r] — the batch is
+//            immutable, so a pending slot's tab_lo/tab_hi are never read.
+//            Equal keys atomicMax the slot so the smallest row wins; an
+//            empty slot is claimed by CAS, and a lost CAS re-examines the
+//            same slot with the value the CAS returned.  A slot's key
+//            identity is fixed once claimed and slots are never emptied,
+//            so a key cannot land in two slots.  Hits store their code;
+//            pending rows store their slot and set pend[i] = 1.
+//            Plain tab_val loads may be stale within the launch; that is
+//            harmless: a stale -1 is corrected by the CAS's return value,
+//            a stale pending value names another row with the same key,
+//            and no value >= 0 is written during the launch.
+//   count    pending row i is a winner iff tab_val[slot] == -(i+2); mark
+//            pend[i] = 2 and count winners per block chunk.
+//   commit   every block sums the counts of the chunks before it, then
+//            ranks its winners in row order; winner k writes the
+//            slot's key, the dictionary hash arrays at base+k,
+//            first_row[k] = i and, last, tab_val[slot] = base+k.
+//   resolve  the other pending rows read their slot's now-final code.
+//
+// On the all-known path count/commit/resolve only stream the n pend
+// bytes.  Probing stops after nslots probes and raises err[0] (the caller
+// keeps the load factor <= 0.5, so this never triggers in a sound run).
+//
+// Optional front table: the probe bound forces the caller to size the
+// table above for a batch of nothing but new keys, far past the caches
+// for a large batch.  A caller may keep the keys it knows for certain in
+// a second, compact table of the same layout ("front", read-only here):
+// claim probes it first as k_ht_probe would and only its misses touch the
+// open table.  A key is in at most one of the two.
+
+#define PW_HT_ERR_PROBE 1     // table full / probe bound hit
+#define PW_HT_ERR_STATE 2     // slot or claimer row out of range
+#define PW_HT_ERR_CAPACITY 4  // dictionary arrays or byte arena too small
+
+__global__ void k_ht_intern_claim(const int64_t* __restrict__ qlo,
+                                  const int64_t* __restrict__ qhi, int64_t n,
+                                  const int64_t* tab_lo, const int64_t* tab_hi,
+                                  long long* tab_val, int64_t nslots,
+                                  const int64_t* __restrict__ front_lo,
+                                  const int64_t* __restrict__ front_hi,
+                                  const long long* __restrict__ front_val,
+                                  int64_t front_nslots,
+                                  int64_t* __restrict__ codes,
+                                  uint8_t* __restrict__ pend, long long* err) {
+  const uint64_t mask = (uint64_t)(nslots - 1);
+  const uint64_t fmask = (uint64_t)(front_nslots - 1);
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (; i < n; i += stride) {
+    const int64_t lo = qlo[i], hi = qhi[i];
+    if (front_nslots) {
+      uint64_t fs = (uint64_t)lo & fmask;
+      long long fv = -1;
+      for (int64_t probes = 0; probes < front_nslots; ++probes) {
+        fv = front_val[fs];
+        if (fv < 0 || (front_lo[fs] == lo && front_hi[fs] == hi)) break;
+        fs = (fs + 1) & fmask;
+        fv = -1;
+      }
+      if (fv >= 0) {
+        codes[i] = (int64_t)fv;
+        pend[i] = 0;
+        continue;
+      }
+    }
+    const long long me = -(long long)(i + 2);
+    uint64_t slot = (uint64_t)lo & mask;
+    int64_t out = -1;
+    uint8_t p = 0;
+    int e = PW_HT_ERR_PROBE;
+    long long tv = tab_val[slot];
+    for (int64_t probes = 0; probes < nslots; ++probes) {
+      if (tv == -1) {
+        tv = (long long)atomicCAS((unsigned long long*)&tab_val[slot],
+                                  (unsigned long long)(long long)-1,
+                                  (unsigned long long)me);
+        if (tv == -1) {  // claimed
+          out = (int64_t)slot, p = 1, e = 0;
+          break;
+        }
+      }
+      if (tv >= 0) {
+        if (tab_lo[slot] == lo && tab_hi[slot] == hi) {
+          out = (int64_t)tv, e = 0;
+          break;
+        }
+      } else {
+        const int64_t r = -(tv + 2);
+        if (r < 0 || r >= n) {
+          e = PW_HT_ERR_STATE;
+          break;
+        }
+        if (qlo[r] == lo && qhi[r] == hi) {
+          if (me > tv)
+            __hip_atomic_fetch_max(&tab_val[slot], me, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+          out = (int64_t)slot, p = 1, e = 0;
+          break;
+        }
+      }
+      slot = (slot + 1) & mask;
+      tv = tab_val[slot];
+    }
+    if (e) atomicOr((unsigned long long*)err, (unsigned long long)e);
+    codes[i] = out;
+    pend[i] = p;
+  }
+}
+
+// rows [start, end) of one block, 16 rows (one pend granule) per lane
+__global__ void k_ht_intern_count(int64_t n, int64_t chunk,
+                                  const int64_t* __restrict__ codes,
+                                  uint8_t* pend, const long long* tab_val,
+                                  int64_t nslots, long long* block_counts,
+                                  long long* err) {
+  __shared__ int cnt;
+  if (threadIdx.x == 0) cnt = 0;
+  __syncthreads();
+  int64_t start = (int64_t)blockIdx.x * chunk;
+  int64_t end = min(start + chunk, n);
+  int local = 0;
+  for (int64_t tile = start; tile < end; tile += (int64_t)blockDim.x * 16) {
+    int64_t g = tile + (int64_t)threadIdx.x * 16;
+    if (g >= end) continue;
+    if (g + 16 <= end) {  // chunk and pend base are 16B-aligned
+      uint4 v = *(const uint4*)(pend + g);
+      if ((v.x | v.y | v.z | v.w) == 0) continue;
+    }
+    for (int64_t i = g; i < min(g + 16, end); ++i) {
+      if (!pend[i]) continue;
+      int64_t slot = codes[i];
+      if (slot < 0 || slot >= nslots) {
+        atomicOr((unsigned long long*)err, (unsigned long long)PW_HT_ERR_STATE);
+        pend[i] = 0;
+        continue;
+      }
+      if (tab_val[slot] == -(long long)(i + 2)) {
+        pend[i] = 2;
+        ++local;
+      }
+    }
+  }
+  if (local) atomicAdd(&cnt, local);
+  __syncthreads();
+  if (threadIdx.x == 0) block_counts[blockIdx.x] = cnt;
+}
+
+__global__ void k_ht_intern_commit(
+    const int64_t* __restrict__ qlo, const int64_t* __restrict__ qhi,
+    int64_t n, int64_t chunk, int64_t* codes, const uint8_t* __restrict__ pend,
+    const long long* __restrict__ block_counts,
+    const long long* __restrict__ base_ptr, int64_t* tab_lo, int64_t* tab_hi,
+    long long* tab_val, int64_t* pool_lo, int64_t* pool_hi, int64_t pool_cap,
+    int64_t* first_row, long long* n_new, long long* err) {
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  __shared__ unsigned long long cursor;
+  __shared__ int wave_tot[PW_BLOCK / 64];
+  // this block's first rank: the winners of the blocks before it (at most
+  // 2048 counts, so every block sums them itself — no scan launch)
+  if (threadIdx.x == 0) cursor = 0;
+  __syncthreads();
+  unsigned long long part = 0;
+  for (int j = threadIdx.x; j < (int)blockIdx.x; j += blockDim.x)
+    part += (unsigned long long)block_counts[j];
+  if (part) atomicAdd(&cursor, part);
+  __syncthreads();
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0)
+    n_new[0] = (long long)cursor + block_counts[blockIdx.x];
+  const long long base = base_ptr[0];
+  int64_t start = (int64_t)blockIdx.x * chunk;
+  int64_t end = min(start + chunk, n);
+  for (int64_t tile = start; tile < end; tile += (int64_t)blockDim.x * 16) {
+    int64_t g = tile + (int64_t)threadIdx.x * 16;
+    unsigned wmask = 0;
+    if (g < end) {
+      bool any = true;
+      if (g + 16 <= end) {
+        uint4 v = *(const uint4*)(pend + g);
+        any = (v.x | v.y | v.z | v.w) != 0;
+      }
+      if (any)
+        for (int j = 0; j < 16 && g + j < end; ++j)
+          if (pend[g + j] == 2) wmask |= 1u << j;
+    }
+    int hits = __popc(wmask);
+    int incl = hits;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      int v = __shfl_up(incl, off, 64);
+      if (lane >= off) incl += v;
+    }
+    if (lane == 63) wave_tot[wave] = incl;
+    __syncthreads();
+    int wbase = 0;
+    for (int w = 0; w < wave; ++w) wbase += wave_tot[w];
+    long long k = (long long)cursor + wbase + (incl - hits);
+    while (wmask) {
+      int j = __ffs(wmask) - 1;
+      wmask &= wmask - 1;
+      const int64_t i = g + j;
+      const int64_t slot = codes[i];  // range-checked by k_ht_intern_count
+      const long long code = base + k;
+      if (code < 0 || code >= pool_cap) {
+        atomicOr((unsigned long long*)err,
+                 (unsigned long long)PW_HT_ERR_CAPACITY);
+      } else {
+        const int64_t lo = qlo[i], hi = qhi[i];
+        tab_lo[slot] = lo;
+        tab_hi[slot] = hi;
+        pool_lo[code] = lo;
+        pool_hi[code] = hi;
+        first_row[k] = i;  // k < winners <= n
+        tab_val[slot] = code;
+        codes[i] = code;
+      }
+      ++k;
+    }
+    __syncthreads();
+    if (threadIdx.x == (int)blockDim.x - 1) cursor += wbase + incl;
+    __syncthreads();
+  }
+}
+
+__global__ void k_ht_intern_resolve(int64_t n, int64_t chunk, int64_t* codes,
+                                    const uint8_t* __restrict__ pend,
+                                    const long long* __restrict__ tab_val) {
+  int64_t start = (int64_t)blockIdx.x * chunk;
+  int64_t end = min(start + chunk, n);
+  for (int64_t tile = start; tile < end; tile += (int64_t)blockDim.x * 16) {
+    int64_t g = tile + (int64_t)threadIdx.x * 16;
+    if (g >= end) continue;
+    if (g + 16 <= end) {
+      uint4 v = *(const uint4*)(pend + g);
+      if ((v.x | v.y | v.z | v.w) == 0) continue;
+    }
+    for (int64_t i = g; i < min(g + 16, end); ++i) {
+      if (pend[i] != 1) continue;
+      long long tv = tab_val[codes[i]];
+      codes[i] = tv >= 0 ? (int64_t)tv : -1;  // < 0 only after a flagged error
+    }
+  }
+}
+
+static inline int64_t pw_intern_chunk(int64_t n, int64_t nblocks) {
+  int64_t chunk = ((n + nblocks - 1) / nblocks + 15) & ~(int64_t)15;
+  return chunk < 16 ? 16 : chunk;
+}
+
+// One call enqueues the four launches.  nblocks (<= 2048) is the number
+// of row chunks of count/commit/resolve; block_counts has nblocks entries,
+// n_new one.
+extern "C" int pw_ht_intern(const void* qlo, const void* qhi, int64_t n,
+                            void* tab_lo, void* tab_hi, void* tab_val,
+                            int64_t nslots, const void* front_lo,
+                            const void* front_hi, const void* front_val,
+                            int64_t front_nslots, const void* base_ptr,
+                            void* pool_lo, void* pool_hi, int64_t pool_cap,
+                            void* codes, void* pend, void* first_row,
+                            void* block_counts, int64_t nblocks, void* n_new,
+                            void* err, void* stream) {
+  if (n <= 0 || nblocks < 1 || nblocks > 2048) return -2;
+  if (nslots < 1 || (nslots & (nslots - 1))) return -2;
+  if (front_nslots < 0 || (front_nslots & (front_nslots - 1))) return -2;
+  hipStream_t s = (hipStream_t)stream;
+  int64_t cblocks = (n + PW_BLOCK - 1) / PW_BLOCK;
+  if (cblocks > 4096) cblocks = 4096;
+  int64_t chunk = pw_intern_chunk(n, nblocks);
+  hipLaunchKernelGGL(k_ht_intern_claim, dim3((uint32_t)cblocks),
+                     dim3(PW_BLOCK), 0, s, (const int64_t*)qlo,
+                     (const int64_t*)qhi, n, (const int64_t*)tab_lo,
+                     (const int64_t*)tab_hi, (long long*)tab_val, nslots,
+                     (const int64_t*)front_lo, (const int64_t*)front_hi,
+                     (const long long*)front_val, front_nslots,
+                     (int64_t*)codes, (uint8_t*)pend, (long long*)err);
+  hipLaunchKernelGGL(k_ht_intern_count, dim3((uint32_t)nblocks),
+                     dim3(PW_BLOCK), 0, s, n, chunk, (const int64_t*)codes,
+                     (uint8_t*)pend, (const long long*)tab_val, nslots,
+                     (long long*)block_counts, (long long*)err);
+  hipLaunchKernelGGL(k_ht_intern_commit, dim3((uint32_t)nblocks),
+                     dim3(PW_BLOCK), 0, s, (const int64_t*)qlo,
+                     (const int64_t*)qhi, n, chunk, (int64_t*)codes,
+                     (const uint8_t*)pend, (const long long*)block_counts,
+                     (const long long*)base_ptr, (int64_t*)tab_lo,
+                     (int64_t*)tab_hi, (long long*)tab_val, (int64_t*)pool_lo,
+                     (int64_t*)pool_hi, pool_cap, (int64_t*)first_row,
+                     (long long*)n_new, (long long*)err);
+  hipLaunchKernelGGL(k_ht_intern_resolve, dim3((uint32_t)nblocks),
+                     dim3(PW_BLOCK), 0, s, n, chunk, (int64_t*)codes,
+                     (const uint8_t*)pend, (const long long*)tab_val);
+  return (int)hipGetLastError();
+}
+
+// Pack the byte spans of the batch's new tokens into the dictionary's
+// arena.  Token k (k < *n_new) is row first_row[k]; its bytes go to a
+// range reserved with one cursor atomicAdd per wave (wave scan of the
+// lengths), and (offset, length) are recorded at code base+k, so the
+// arena layout may vary run to run while the decoded strings do not.
+__global__ void k_gather_spans(const uint8_t* __restrict__ buf, int64_t nbuf,
+                               const int64_t* __restrict__ starts,
+                               const int64_t* __restrict__ ends, int64_t nrows,
+                               const int64_t* __restrict__ first_row,
+                               const long long* __restrict__ n_new_ptr,
+                               const long long* __restrict__ base_ptr,
+                               uint8_t* arena, int64_t arena_cap,
+                               unsigned long long* cursor, int64_t* tok_off,
+                               int64_t* tok_len, int64_t pool_cap,
+                               long long* err) {
+  const int lane = threadIdx.x & 63;
+  long long n_new = n_new_ptr[0];
+  if (n_new > nrows) n_new = nrows;
+  const long long base = base_ptr[0];
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  // whole waves iterate together (the bound is rounded up per wave)
+  const int64_t k0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (int64_t k = k0; k - lane < n_new; k += stride) {
+    int64_t s = 0, len = 0;
+    bool ok = k < n_new && base + k >= 0 && base + k < pool_cap;
+    if (ok) {
+      int64_t row = first_row[k];
+      ok = row >= 0 && row < nrows;
+      if (ok) {
+        s = starts[row];
+        int64_t e = ends[row];
+        ok = s >= 0 && e >= s && e <= nbuf;
+        len = ok ? e - s : 0;
+      }
+    }
+    if (k < n_new && !ok)
+      atomicOr((unsigned long long*)err,
+               (unsigned long long)(base + k < pool_cap ? PW_HT_ERR_STATE
+                                                        : PW_HT_ERR_CAPACITY));
+    long long incl = len;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      long long v = __shfl_up(incl, off, 64);
+      if (lane >= off) incl += v;
+    }
+    long long total = __shfl(incl, 63, 64);
+    unsigned long long wbase = 0;
+    if (lane == 0 && total) wbase = atomicAdd(cursor, (unsigned long long)total);
+    wbase = __shfl(wbase, 0, 64);
+    if (!ok) continue;
+    int64_t off = (int64_t)wbase + (incl - len);
+    if (off + len > arena_cap) {
+      atomicOr((unsigned long long*)err,
+               (unsigned long long)PW_HT_ERR_CAPACITY);
+      off = 0, len = 0;
+    }
+    for (int64_t b = 0; b < len; ++b) arena[off + b] = buf[s + b];
+    tok_off[base + k] = off;
+    tok_len[base + k] = len;
+  }
+}
+
+extern "C" int pw_gather_spans(const void* buf, int64_t nbuf,
+                               const void* starts, const void* ends,
+                               int64_t nrows, const void* first_row,
+                               const void* n_new_ptr, const void* base_ptr,
+                               void* arena, int64_t arena_cap, void* cursor,
+                               void* tok_off, void* tok_len, int64_t pool_cap,
+                               void* err, void* stream) {
+  if (nrows <= 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_gather_spans, dim3(pw_grid(nrows) > 256 ? 256 : pw_grid(nrows)),
+                     dim3(PW_BLOCK), 0, s, (const uint8_t*)buf, nbuf,
+                     (const int64_t*)starts, (const int64_t*)ends, nrows,
+                     (const int64_t*)first_row, (const long long*)n_new_ptr,
+                     (const long long*)base_ptr, (uint8_t*)arena, arena_cap,
+                     (unsigned long long*)cursor, (int64_t*)tok_off,
+                     (int64_t*)tok_len, pool_cap, (long long*)err);
+  return (int)hipGetLastError();
+}
+
 extern "C" int pw_gather_cols(const void* idx, int64_t m, int ncols,
                               void* const* srcs, void* const* dsts,
                               void* stream) {
