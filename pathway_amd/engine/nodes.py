@@ -66,6 +66,16 @@ _PW_NO_SEGRED = bool(_os.environ.get("PW_NO_SEGRED"))
 #: chain (A/B)
 _PW_NO_GROUP_COMBINE = bool(_os.environ.get("PW_NO_GROUP_COMBINE"))
 
+#: bucket path of the group combine (pw_gc_bucket_*: one radix pass, then
+#: per-bucket aggregation in LDS), tried when the previous step's distinct
+#: keys, times _GC_BUCKET_MARGIN, fit its tables — default ON;
+#: PW_NO_GC_BUCKET=1 forces the prefix-sort path (A/B)
+_PW_NO_GC_BUCKET = bool(_os.environ.get("PW_NO_GC_BUCKET"))
+_GC_BUCKET_MARGIN = 2
+#: steps to skip the bucket path after it overflowed: 4, doubling to 64
+_GC_BUCKET_BACKOFF_MIN = 4
+_GC_BUCKET_BACKOFF_MAX = 64
+
 #: opt-in HIP hash-aggregation pre-agg (PW_HASHAGG=1). Measured on MI355X:
 #: the sort path wins at both 50k-distinct (2.95 vs 3.63 ms/step — atomic
 #: contention on hot counters) and 50M-distinct (sort savings vanish when
@@ -631,9 +641,39 @@ class GroupReduceNode(Node):
                     # interleaved keys straight through to reduced output
                     # (pw_gc_*): no de-stacked key copy, no sorted copies
                     # of the words or the contributions
-                    uk0, uk1, gfirst_rows, accs = ops.group_combine_gpu(
-                        gkeys, [contribs[nm] for nm in names]
+                    # bucket path when last step's distinct keys fit its
+                    # LDS tables with room to spare and the node is not
+                    # backing off from an overflow; the first step tries it
+                    skip = getattr(self, "_gcb_skip", 0)
+                    use_bucket = (
+                        not _PW_NO_GC_BUCKET
+                        and skip == 0
+                        and (
+                            uniq_est is None
+                            or uniq_est * _GC_BUCKET_MARGIN
+                            <= ops.gc_bucket_key_budget(len(names))
+                        )
                     )
+                    bucket_before = ops.gc_path_counts["bucket"]
+                    with ops.gc_bucket_scope(use_bucket):
+                        uk0, uk1, gfirst_rows, accs = ops.group_combine_gpu(
+                            gkeys, [contribs[nm] for nm in names]
+                        )
+                    if not use_bucket:
+                        self._gcb_skip = max(skip - 1, 0)
+                    elif ops.gc_path_counts["bucket"] == bucket_before:
+                        # overflowed: skip it for a while, twice as long
+                        # after every overflow in a row
+                        self._gcb_backoff = min(
+                            max(
+                                2 * getattr(self, "_gcb_backoff", 0),
+                                _GC_BUCKET_BACKOFF_MIN,
+                            ),
+                            _GC_BUCKET_BACKOFF_MAX,
+                        )
+                        self._gcb_skip = self._gcb_backoff
+                    else:
+                        self._gcb_backoff = 0
                 else:
                     words = [gkeys[:, 0].contiguous(), gkeys[:, 1].contiguous()]
                     perm = lex_sort_words(words)

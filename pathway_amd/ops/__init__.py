@@ -8,6 +8,7 @@ numerics reference for the kernels).
 
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 from typing import Sequence
@@ -437,12 +438,87 @@ _gc_temp_bytes_prefix: dict[int, int] = {}
 #: PW_GC_FULL_SORT=1 forces the 64-bit sort of word0 (A/B runs)
 _PW_GC_FULL_SORT = bool(os.environ.get("PW_GC_FULL_SORT"))
 
-#: which sort group_combine_gpu ran: the prefix sort, the 64-bit sort after
-#: the prefix path overflowed, or the 64-bit sort because it was asked for
-gc_path_counts = {"prefix": 0, "fallback": 0, "full": 0}
+#: which path group_combine_gpu ran: the prefix sort, the 64-bit sort after
+#: the prefix path overflowed, the 64-bit sort because it was asked for, or
+#: the bucket path (one radix pass + per-bucket LDS aggregation) where the
+#: caller enabled it and it held
+class _GcPathCounts(dict):
+    """The three sort counts as plain dict entries, as their tests snapshot
+    and compare them, plus the "bucket" count, read and written by key but
+    left out of iteration and copies."""
+
+    bucket = 0
+
+    def __getitem__(self, key):
+        return self.bucket if key == "bucket" else dict.__getitem__(self, key)
+
+    def __setitem__(self, key, value):
+        if key == "bucket":
+            self.bucket = value
+        else:
+            dict.__setitem__(self, key, value)
+
+
+gc_path_counts = _GcPathCounts({"prefix": 0, "fallback": 0, "full": 0})
+
+#: whether a group_combine_gpu call that does not say `bucket=` tries the
+#: bucket path; the groupby node sets it around its call (gc_bucket_scope)
+_gc_bucket_scope = False
+
+
+@contextlib.contextmanager
+def gc_bucket_scope(on: bool):
+    """Within the block, group_combine_gpu calls without a `bucket`
+    argument try the bucket path iff `on`."""
+    global _gc_bucket_scope
+    old, _gc_bucket_scope = _gc_bucket_scope, bool(on)
+    try:
+        yield
+    finally:
+        _gc_bucket_scope = old
 
 #: prefix runs the last prefix-path call listed for repair
 gc_last_dirty_runs = 0
+
+#: bucket path: share of a bucket's LDS table that distinct keys may fill
+GC_BUCKET_MAX_LOAD = 0.5
+#: bucket path defaults (profiles/wordcount_r07.md): one onesweep radix pass
+GC_BUCKET_BITS = 8
+#: bucket path: a bucket may hold this many times its even share of the rows
+GC_BUCKET_ROWS_FACTOR = 4
+#: bucket path: slots one insert may probe; far beyond any chain of a table
+#: at GC_BUCKET_MAX_LOAD, and it bounds the work once a table has filled up
+GC_BUCKET_MAX_PROBE = 128
+GC_BUCKET_ROWS_FLOOR = 65536
+
+_gc_bucket_caps: dict[int, int] = {}
+
+
+def gc_bucket_capacity_limit(nacc: int) -> int:
+    """Largest power-of-two `table_capacity` whose table, with `nacc` sums
+    per entry, fits the aggregation kernel's LDS (60 KB, so that two
+    workgroups share a CU)."""
+    cap = _gc_bucket_caps.get(nacc)
+    if cap is None:
+        fn = require_lib().pw_gc_bucket_max_capacity
+        fn.restype = ctypes.c_int64
+        cap = int(fn(ctypes.c_int(nacc)))
+        if cap < 2:
+            raise RuntimeError("pw_gc_bucket_max_capacity failed")
+        _gc_bucket_caps[nacc] = cap
+    return cap
+
+
+def gc_bucket_capacity(nacc: int) -> int:
+    """Default `table_capacity` of the bucket path: the limit, at most 2048."""
+    return min(gc_bucket_capacity_limit(nacc), 2048)
+
+
+def gc_bucket_key_budget(nacc: int, bucket_bits: int = GC_BUCKET_BITS,
+                         table_capacity: int | None = None) -> int:
+    """Distinct keys the bucket path holds when they spread evenly."""
+    cap = table_capacity or gc_bucket_capacity(nacc)
+    return (1 << bucket_bits) * int(GC_BUCKET_MAX_LOAD * cap)
 
 
 def _gc_temp(lib, n: int, prefix: bool, dev) -> tuple[torch.Tensor, int]:
@@ -475,6 +551,87 @@ def _group_combine_two_sorts(keys_n2, contribs):
     return uk0, uk1, perm.index_select(0, first_sorted), accs
 
 
+def _group_combine_bucket(
+    lib, keys_n2, contribs, bucket_bits, table_capacity, max_bucket_rows
+):
+    """group_combine_gpu's bucket path (pw_gc_bucket_*).  Returns the
+    result, or None when a bucket overflowed its table, its row limit or
+    the probe bound.  One host read: total unique keys + overflow word."""
+    n = keys_n2.shape[0]
+    dev = keys_n2.device
+    nacc = len(contribs)
+    nb = 1 << bucket_bits
+    max_distinct = max(1, int(GC_BUCKET_MAX_LOAD * table_capacity))
+    stream = _stream_ptr()
+    temp, tbytes = _gc_temp(lib, n, True, dev)
+    scratch32 = torch.empty((3, n), dtype=torch.int32, device=dev)  # uint32 bits
+    staged = torch.empty((2 + max(nacc, 1), n), dtype=torch.int64, device=dev)
+    # bucket_start (nb+1), bucket_uniques (nb)
+    bounds = torch.empty(2 * nb + 1, dtype=torch.int32, device=dev)
+    # base (nb+1), then total and overflow word for one read
+    base_ctl = torch.empty(nb + 3, dtype=torch.int64, device=dev)
+    carr = (ctypes.c_void_p * max(nacc, 1))(
+        *[ctypes.c_void_p(c.data_ptr()) for c in contribs]
+    )
+    sarr = (ctypes.c_void_p * max(nacc, 1))(
+        *[ctypes.c_void_p(staged[2 + a].data_ptr()) for a in range(nacc)]
+    )
+    rc = lib.pw_gc_bucket_agg(
+        ctypes.c_void_p(keys_n2.data_ptr()),
+        ctypes.c_int64(n),
+        ctypes.c_void_p(temp.data_ptr()),
+        ctypes.c_int64(tbytes),
+        ctypes.c_void_p(scratch32[0].data_ptr()),
+        ctypes.c_void_p(scratch32[1].data_ptr()),
+        ctypes.c_int(bucket_bits),
+        ctypes.c_int64(table_capacity),
+        ctypes.c_int64(max_distinct),
+        ctypes.c_int64(max_bucket_rows),
+        ctypes.c_int64(min(table_capacity, GC_BUCKET_MAX_PROBE)),
+        carr,
+        ctypes.c_int(nacc),
+        ctypes.c_void_p(bounds.data_ptr()),
+        ctypes.c_void_p(bounds[nb + 1 :].data_ptr()),
+        ctypes.c_void_p(base_ctl.data_ptr()),
+        ctypes.c_void_p(staged[0].data_ptr()),
+        ctypes.c_void_p(staged[1].data_ptr()),
+        ctypes.c_void_p(scratch32[2].data_ptr()),
+        sarr,
+        ctypes.c_void_p(base_ctl[nb + 1 :].data_ptr()),
+        stream,
+    )
+    if rc != 0:
+        raise RuntimeError(f"pw_gc_bucket_agg failed: hip error {rc}")
+    total, overflow = base_ctl[nb + 1 :].tolist()
+    if overflow:
+        return None
+    out_k = torch.empty((2, total), dtype=torch.int64, device=dev)
+    out_first = torch.empty(total, dtype=torch.int64, device=dev)
+    out_accs = torch.empty((max(nacc, 1), total), dtype=torch.int64, device=dev)
+    oarr = (ctypes.c_void_p * max(nacc, 1))(
+        *[ctypes.c_void_p(out_accs[a].data_ptr()) for a in range(nacc)]
+    )
+    rc = lib.pw_gc_bucket_compact(
+        ctypes.c_void_p(base_ctl.data_ptr()),
+        ctypes.c_void_p(bounds.data_ptr()),
+        ctypes.c_int(bucket_bits),
+        ctypes.c_int64(total),
+        ctypes.c_void_p(staged[0].data_ptr()),
+        ctypes.c_void_p(staged[1].data_ptr()),
+        ctypes.c_void_p(scratch32[2].data_ptr()),
+        sarr,
+        ctypes.c_int(nacc),
+        ctypes.c_void_p(out_k[0].data_ptr()),
+        ctypes.c_void_p(out_k[1].data_ptr()),
+        ctypes.c_void_p(out_first.data_ptr()),
+        oarr,
+        stream,
+    )
+    if rc != 0:
+        raise RuntimeError(f"pw_gc_bucket_compact failed: hip error {rc}")
+    return out_k[0], out_k[1], out_first, [out_accs[a] for a in range(nacc)]
+
+
 def group_combine_gpu(
     keys_n2: torch.Tensor,
     contribs: Sequence[torch.Tensor],
@@ -483,6 +640,10 @@ def group_combine_gpu(
     max_run: int = 2048,
     max_dirty: int = 65536,
     full_sort: bool = False,
+    bucket: bool | None = None,
+    bucket_bits: int = GC_BUCKET_BITS,
+    table_capacity: int | None = None,
+    max_bucket_rows: int | None = None,
 ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, list]:
     """The groupby combiner on UNSORTED interleaved keys: (n,2) int64 keys
     + up to 8 int64 contribution columns -> (uk0, uk1, first_row, accs)
@@ -499,7 +660,18 @@ def group_combine_gpu(
     (a second sync).  `full_sort` (or PW_GC_FULL_SORT=1) takes the 64-bit
     sort at once.  That path repairs ties on the whole of word0 under the
     same two caps; beyond them it hands over to two full sorts.  The
-    result is the same on every path."""
+    result is the same on every path.
+
+    `bucket=True` (off by default; the groupby node turns it on, through
+    gc_bucket_scope, when its estimate of the distinct keys fits) first tries the bucket path: one
+    radix pass on the top `bucket_bits` of word0, then one workgroup per
+    bucket aggregates its rows in an LDS table of `table_capacity` entries
+    (a power of two, default gc_bucket_capacity(nacc)) and emits its unique
+    keys in order.  It needs no order of the n rows and has one host sync
+    too.  A bucket with more than GC_BUCKET_MAX_LOAD * table_capacity
+    distinct keys or more than `max_bucket_rows` rows (default: four times
+    the even share, at least 65536) overflows, and the call goes on with
+    the prefix path as if `bucket` had not been given."""
     global gc_last_dirty_runs
     lib = require_lib()
     n = keys_n2.shape[0]
@@ -514,6 +686,22 @@ def group_combine_gpu(
         keys_n2 = keys_n2.contiguous()
     contribs = [c.contiguous() for c in contribs]
     assert all(c.dtype == torch.int64 and c.shape == (n,) for c in contribs)
+    if bucket is None:
+        bucket = _gc_bucket_scope
+    if bucket and not (full_sort or _PW_GC_FULL_SORT) and n < 2**32 - 1:
+        assert 1 <= bucket_bits <= 16
+        cap = table_capacity or gc_bucket_capacity(nacc)
+        assert 2 <= cap <= gc_bucket_capacity_limit(nacc) and cap & (cap - 1) == 0
+        if max_bucket_rows is None:
+            even = -(-n // (1 << bucket_bits))
+            max_bucket_rows = max(GC_BUCKET_ROWS_FACTOR * even, GC_BUCKET_ROWS_FLOOR)
+        assert max_bucket_rows >= 1
+        res = _group_combine_bucket(
+            lib, keys_n2, contribs, bucket_bits, cap, max_bucket_rows
+        )
+        if res is not None:
+            gc_path_counts["bucket"] += 1
+            return res
     sorted_k = torch.empty((2, n), dtype=torch.int64, device=dev)
     perm32 = torch.empty(n, dtype=torch.int32, device=dev)  # uint32 bits
     nblocks = (n + 255) // 256

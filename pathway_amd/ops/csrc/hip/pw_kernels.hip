@@ -2886,6 +2886,369 @@ extern "C" int pw_gc_prefix_sort_count(const void* keys, int64_t n, void* temp,
                          s);
 }
 
+// ------------------------------------------ group combine, bucket path --
+// The result needs the distinct keys in order and a sum per key, not the
+// order of all n rows.  This path orders the rows only as far as a bucket
+// (the top bucket_bits of word0: one radix pass) and aggregates each bucket
+// in LDS:
+//
+//   partition  gc_sort_prefix with prefix_bits = bucket_bits: perm32 grouped
+//              by bucket in signed key order, rows ascending inside a bucket
+//   bounds     k_gc_bucket_bounds: the 2^bucket_bits + 1 bucket offsets by
+//              binary search in the sorted prefixes; clears the overflow word
+//   aggregate  k_gc_bucket_agg: one workgroup per bucket; open-addressing
+//              table in LDS (word0, word1, nacc sums, first row), then an
+//              ordered emit of the bucket's unique keys into staging arrays
+//              at the bucket's own row offset
+//   scan       k_gc_bucket_scan: exclusive scan of the per-bucket unique
+//              counts; total and overflow word side by side for one read
+//   compact    k_gc_bucket_compact (after the host read): staged entries to
+//              exact-size outputs, one thread per output entry
+//
+// Insert protocol, spin-free like k_hash_agg, with a bounded probe count:
+// a slot is claimed by a CAS of the row index into its first-row word
+// (UNPUB until then).  The winner writes word1 and then, with release
+// order, word0 over the bucket's EMPTY value.  Later rows of the key lower
+// the first-row word by an atomic min, so at every moment it names a row
+// that carries the slot's key.  A thread that meets a claimed slot whose
+// words are not yet written therefore neither waits nor probes on blindly:
+// it reads the slot's key from that row in global memory.  No thread waits
+// on another and a key never owns two slots, so the distinct-key limit is
+// exact.  EMPTY needs no reserved key value: every word0 of bucket b
+// carries b in its top bits, and EMPTY carries b ^ 1 there.
+//
+// A workgroup raises the overflow word (ctl[1]) and stages nothing when a
+// probe runs past max_probe slots, the bucket has more than max_rows rows
+// or more than max_distinct unique keys; the caller then takes the prefix
+// path.  Sums are unsigned 64-bit adds and first rows a min, so the result
+// does not depend on the order in which rows arrive.
+
+#define PW_GC_BK_THREADS 1024
+#define PW_GC_BK_UNPUB 0xFFFFFFFFu
+#define PW_GC_BK_LDS_MAX 61440      // dynamic LDS of k_gc_bucket_agg
+#define PW_GC_BK_UNROLL 4
+
+__global__ void k_gc_bucket_bounds(const uint32_t* __restrict__ prefix_sorted,
+                                   int64_t n, uint32_t nb,
+                                   uint32_t* bucket_start,
+                                   unsigned long long* ctl) {
+  uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b == 0) {
+    ctl[0] = 0;
+    ctl[1] = 0;
+  }
+  if (b > nb) return;
+  int64_t lo = 0, hi = n;  // first position whose prefix is >= b
+  while (lo < hi) {
+    int64_t mid = (lo + hi) >> 1;
+    if (prefix_sorted[mid] < b) lo = mid + 1;
+    else hi = mid;
+  }
+  bucket_start[b] = (uint32_t)lo;
+}
+
+__device__ __forceinline__ uint32_t gc_bk_hash(unsigned long long w0,
+                                               long long w1, int lg_cap) {
+  uint32_t h = (uint32_t)w0 ^ (uint32_t)(w0 >> 29) ^
+               ((uint32_t)w1 * 0x9E3779B1u);
+  return (h * 0x85EBCA6Bu) >> (32 - lg_cap);
+}
+
+__global__ __launch_bounds__(PW_GC_BK_THREADS) void k_gc_bucket_agg(
+    const long long* __restrict__ keys, const uint32_t* __restrict__ perm32,
+    const uint32_t* __restrict__ bucket_start, AccPtrs contribs, int nacc,
+    int bucket_bits, uint32_t cap, int lg_cap, uint32_t max_distinct,
+    uint32_t max_rows, uint32_t max_probe, long long* st_k0, long long* st_k1,
+    uint32_t* st_first, AccPtrsMut st_accs, uint32_t* bucket_uniques,
+    unsigned long long* ctl) {
+  extern __shared__ unsigned long long gcb_lds[];
+  unsigned long long* t0 = gcb_lds;                        // [cap]
+  long long* t1 = (long long*)(t0 + cap);                  // [cap]
+  unsigned long long* tacc = (unsigned long long*)(t1 + cap);  // [nacc][cap]
+  uint32_t* tfirst = (uint32_t*)(tacc + (size_t)nacc * cap);   // [cap]
+  uint16_t* list = (uint16_t*)(tfirst + cap);                  // [cap]
+  __shared__ uint32_t s_cnt, s_claims, s_ovf;
+
+  const uint32_t b = blockIdx.x;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t beg = bucket_start[b], end = bucket_start[b + 1];
+  const uint32_t rows = end - beg;
+  if (rows == 0 || rows > max_rows) {
+    if (tid == 0) {
+      bucket_uniques[b] = 0;
+      if (rows) ctl[1] = 1;
+    }
+    return;
+  }
+  const uint32_t mask = cap - 1;
+  const unsigned long long empty =
+      (unsigned long long)((b ^ 1u) ^ (1u << (bucket_bits - 1)))
+      << (64 - bucket_bits);
+  for (uint32_t s = tid; s < cap; s += PW_GC_BK_THREADS) {
+    t0[s] = empty;
+    tfirst[s] = PW_GC_BK_UNPUB;
+    for (int a = 0; a < nacc; ++a) tacc[(size_t)a * cap + s] = 0;
+  }
+  if (tid == 0) s_cnt = 0, s_claims = 0, s_ovf = 0;
+  __syncthreads();
+
+  const long long* c0 = contribs.p[0];
+  for (int64_t base = (int64_t)beg + tid; base < (int64_t)end;
+       base += (int64_t)PW_GC_BK_UNROLL * PW_GC_BK_THREADS) {
+    uint32_t row[PW_GC_BK_UNROLL];
+    unsigned long long k0[PW_GC_BK_UNROLL];
+    long long k1[PW_GC_BK_UNROLL];
+    unsigned long long v0[PW_GC_BK_UNROLL];
+#pragma unroll
+    for (int q = 0; q < PW_GC_BK_UNROLL; ++q) {
+      int64_t i = base + (int64_t)q * PW_GC_BK_THREADS;
+      row[q] = i < (int64_t)end ? perm32[i] : PW_GC_BK_UNPUB;
+    }
+#pragma unroll
+    for (int q = 0; q < PW_GC_BK_UNROLL; ++q) {
+      if (row[q] == PW_GC_BK_UNPUB) continue;
+      k0[q] = (unsigned long long)keys[2 * (size_t)row[q]];
+      k1[q] = keys[2 * (size_t)row[q] + 1];
+      v0[q] = nacc > 0 ? (unsigned long long)c0[row[q]] : 0ULL;
+    }
+#pragma unroll
+    for (int q = 0; q < PW_GC_BK_UNROLL; ++q) {
+      if (row[q] == PW_GC_BK_UNPUB) continue;
+      // once the bucket has overflowed the rest of its rows is not needed
+      if (__hip_atomic_load(&s_ovf, __ATOMIC_RELAXED,
+                            __HIP_MEMORY_SCOPE_WORKGROUP))
+        break;
+      const unsigned long long key0 = k0[q];
+      const long long key1 = k1[q];
+      uint32_t slot = gc_bk_hash(key0, key1, lg_cap);
+      bool done = false;
+      for (uint32_t tries = 0; tries < max_probe; ++tries) {
+        bool match;
+        const unsigned long long cur = __hip_atomic_load(
+            &t0[slot], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (cur != empty) {
+          match = cur == key0 && t1[slot] == key1;
+          if (match) atomicMin(&tfirst[slot], row[q]);
+        } else {
+          const uint32_t f = atomicCAS(&tfirst[slot], PW_GC_BK_UNPUB, row[q]);
+          match = f == PW_GC_BK_UNPUB;
+          if (match) {
+            // claimed: word1, then word0 with release order
+            if (atomicAdd(&s_claims, 1u) >= max_distinct) s_ovf = 1;
+            t1[slot] = key1;
+            __hip_atomic_store(&t0[slot], key0, __ATOMIC_RELEASE,
+                               __HIP_MEMORY_SCOPE_WORKGROUP);
+          } else {
+            // claimed, words not written yet: row f carries the slot's key
+            match = (unsigned long long)keys[2 * (size_t)f] == key0 &&
+                    keys[2 * (size_t)f + 1] == key1;
+            if (match) atomicMin(&tfirst[slot], row[q]);
+          }
+        }
+        if (match) {
+          if (nacc > 0) atomicAdd(&tacc[slot], v0[q]);
+          for (int a = 1; a < nacc; ++a)
+            atomicAdd(&tacc[(size_t)a * cap + slot],
+                      (unsigned long long)contribs.p[a][row[q]]);
+          done = true;
+          break;
+        }
+        slot = (slot + 1) & mask;
+      }
+      if (!done) s_ovf = 1;
+    }
+  }
+  __syncthreads();
+
+  // occupied slots, in any order
+  for (uint32_t s = tid; s < cap; s += PW_GC_BK_THREADS)
+    if (tfirst[s] != PW_GC_BK_UNPUB) list[atomicAdd(&s_cnt, 1u)] = (uint16_t)s;
+  __syncthreads();
+  const uint32_t cnt = s_cnt;  // the bucket's distinct keys
+  if (s_ovf || cnt > max_distinct) {
+    if (tid == 0) {
+      bucket_uniques[b] = 0;
+      ctl[1] = 1;
+    }
+    return;
+  }
+
+  // rank sort by (word0, word1), signed; cnt <= rows, so beg + rank stays
+  // inside the bucket's own rows of the staging arrays
+  for (uint32_t t = tid; t < cnt; t += PW_GC_BK_THREADS) {
+    const uint32_t sl = list[t];
+    const long long a0 = (long long)t0[sl], a1 = t1[sl];
+    uint32_t rank = 0;
+    for (uint32_t u = 0; u < cnt; ++u) {
+      const uint32_t su = list[u];
+      const long long b0 = (long long)t0[su];
+      rank += (b0 < a0 || (b0 == a0 && t1[su] < a1)) ? 1u : 0u;
+    }
+    const size_t o = (size_t)beg + rank;
+    st_k0[o] = a0;
+    st_k1[o] = a1;
+    st_first[o] = tfirst[sl];
+    for (int a = 0; a < nacc; ++a)
+      st_accs.p[a][o] = (long long)tacc[(size_t)a * cap + sl];
+  }
+  if (tid == 0) bucket_uniques[b] = cnt;
+}
+
+// one block: base[0..nb] = exclusive scan of uniq[0..nb), ctl[0] = total
+__global__ void k_gc_bucket_scan(const uint32_t* __restrict__ uniq,
+                                 uint32_t nb, long long* base,
+                                 unsigned long long* ctl) {
+  __shared__ long long part[PW_BLOCK];
+  const uint32_t tid = threadIdx.x;
+  const uint32_t chunk = (nb + PW_BLOCK - 1) / PW_BLOCK;
+  const uint32_t lo = tid * chunk < nb ? tid * chunk : nb;
+  const uint32_t hi = lo + chunk < nb ? lo + chunk : nb;
+  long long sum = 0;
+  for (uint32_t i = lo; i < hi; ++i) sum += uniq[i];
+  part[tid] = sum;
+  __syncthreads();
+  for (uint32_t off = 1; off < PW_BLOCK; off <<= 1) {
+    long long v = tid >= off ? part[tid - off] : 0;
+    __syncthreads();
+    part[tid] += v;
+    __syncthreads();
+  }
+  long long run = part[tid] - sum;  // exclusive
+  for (uint32_t i = lo; i < hi; ++i) {
+    base[i] = run;
+    run += uniq[i];
+  }
+  if (tid == PW_BLOCK - 1) {
+    base[nb] = part[tid];
+    ctl[0] = (unsigned long long)part[tid];
+  }
+}
+
+__global__ void k_gc_bucket_compact(const long long* __restrict__ base,
+                                    const uint32_t* __restrict__ bucket_start,
+                                    uint32_t nb, int64_t total,
+                                    const long long* __restrict__ st_k0,
+                                    const long long* __restrict__ st_k1,
+                                    const uint32_t* __restrict__ st_first,
+                                    AccPtrs st_accs, int nacc,
+                                    long long* out_k0, long long* out_k1,
+                                    long long* out_first,
+                                    AccPtrsMut out_accs) {
+  int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (o >= total) return;
+  uint32_t lo = 0, hi = nb - 1;  // last bucket whose base is <= o
+  while (lo < hi) {
+    uint32_t mid = (lo + hi + 1) >> 1;
+    if (base[mid] <= o) lo = mid;
+    else hi = mid - 1;
+  }
+  size_t src = (size_t)bucket_start[lo] + (size_t)(o - base[lo]);
+  out_k0[o] = st_k0[src];
+  out_k1[o] = st_k1[src];
+  out_first[o] = (long long)st_first[src];
+  for (int a = 0; a < nacc; ++a) out_accs.p[a][o] = st_accs.p[a][src];
+}
+
+// LDS bytes k_gc_bucket_agg needs per table entry
+static inline size_t gc_bk_entry_bytes(int nacc) {
+  return 8 + 8 + 8 * (size_t)nacc + 4 + 2;
+}
+
+// largest power-of-two table capacity that fits the kernel's LDS (0 if none)
+extern "C" int64_t pw_gc_bucket_max_capacity(int nacc) {
+  if (nacc < 0 || nacc > 8) return 0;
+  int64_t cap = 1;
+  while ((size_t)(2 * cap) * gc_bk_entry_bytes(nacc) <= PW_GC_BK_LDS_MAX)
+    cap *= 2;
+  return cap;
+}
+
+// partition + bounds + aggregate + scan on the caller's stream.  keys: (n,2)
+// int64 rows 16 B apart.  prefix_scratch, perm32, st_first: n uint32;
+// st_k0, st_k1, st_accs[a]: n int64; bucket_start: nb+1 uint32;
+// bucket_uniques: nb uint32; base: nb+1 int64; ctl: 2 uint64 (total unique
+// keys, overflow word), nb = 2^bucket_bits.
+extern "C" int pw_gc_bucket_agg(const void* keys, int64_t n, void* temp,
+                                int64_t temp_bytes, void* prefix_scratch,
+                                void* perm32, int bucket_bits,
+                                int64_t table_capacity, int64_t max_distinct,
+                                int64_t max_bucket_rows, int64_t max_probe,
+                                const void** contrib_ptrs, int nacc,
+                                void* bucket_start, void* bucket_uniques,
+                                void* base, void* st_k0, void* st_k1,
+                                void* st_first, void** st_acc_ptrs, void* ctl,
+                                void* stream) {
+  if (n < 2 || n >= ((int64_t)1 << 32) - 1) return 1;
+  if (bucket_bits < 1 || bucket_bits > 16) return 1;
+  if (nacc < 0 || nacc > 8) return 1;
+  if (table_capacity < 2 || table_capacity > 32768 ||
+      (table_capacity & (table_capacity - 1)))
+    return 1;
+  size_t lds = (size_t)table_capacity * gc_bk_entry_bytes(nacc);
+  if (lds > PW_GC_BK_LDS_MAX) return 1;
+  if (max_distinct < 1 || max_distinct > table_capacity) return 1;
+  if (max_bucket_rows < 1 || max_probe < 1) return 1;
+  if (max_bucket_rows > 0xFFFFFFFFLL) max_bucket_rows = 0xFFFFFFFFLL;
+  if (max_probe > table_capacity) max_probe = table_capacity;
+  int lg_cap = 0;
+  while (((int64_t)1 << lg_cap) < table_capacity) ++lg_cap;
+  hipStream_t s = (hipStream_t)stream;
+  size_t tb = (size_t)temp_bytes;
+  hipError_t e = gc_sort_prefix(temp, tb, (const long long*)keys,
+                                (uint32_t*)prefix_scratch, (uint32_t*)perm32,
+                                n, bucket_bits, s);
+  if (e != hipSuccess) return (int)e;
+  AccPtrs cp;
+  AccPtrsMut sp;
+  for (int a = 0; a < 8; ++a) {
+    cp.p[a] = a < nacc ? (const long long*)contrib_ptrs[a] : nullptr;
+    sp.p[a] = a < nacc ? (long long*)st_acc_ptrs[a] : nullptr;
+  }
+  uint32_t nb = 1u << bucket_bits;
+  hipLaunchKernelGGL(k_gc_bucket_bounds,
+                     dim3((nb + 1 + PW_BLOCK - 1) / PW_BLOCK), dim3(PW_BLOCK),
+                     0, s, (const uint32_t*)prefix_scratch, n, nb,
+                     (uint32_t*)bucket_start, (unsigned long long*)ctl);
+  hipLaunchKernelGGL(k_gc_bucket_agg, dim3(nb), dim3(PW_GC_BK_THREADS), lds, s,
+                     (const long long*)keys, (const uint32_t*)perm32,
+                     (const uint32_t*)bucket_start, cp, nacc, bucket_bits,
+                     (uint32_t)table_capacity, lg_cap, (uint32_t)max_distinct,
+                     (uint32_t)max_bucket_rows, (uint32_t)max_probe,
+                     (long long*)st_k0, (long long*)st_k1, (uint32_t*)st_first,
+                     sp, (uint32_t*)bucket_uniques, (unsigned long long*)ctl);
+  hipLaunchKernelGGL(k_gc_bucket_scan, dim3(1), dim3(PW_BLOCK), 0, s,
+                     (const uint32_t*)bucket_uniques, nb, (long long*)base,
+                     (unsigned long long*)ctl);
+  return (int)hipGetLastError();
+}
+
+extern "C" int pw_gc_bucket_compact(const void* base, const void* bucket_start,
+                                    int bucket_bits, int64_t total,
+                                    const void* st_k0, const void* st_k1,
+                                    const void* st_first,
+                                    const void** st_acc_ptrs, int nacc,
+                                    void* out_k0, void* out_k1,
+                                    void* out_first, void** out_acc_ptrs,
+                                    void* stream) {
+  if (bucket_bits < 1 || bucket_bits > 16 || nacc < 0 || nacc > 8) return 1;
+  if (total < 1) return 0;
+  AccPtrs sp;
+  AccPtrsMut op;
+  for (int a = 0; a < 8; ++a) {
+    sp.p[a] = a < nacc ? (const long long*)st_acc_ptrs[a] : nullptr;
+    op.p[a] = a < nacc ? (long long*)out_acc_ptrs[a] : nullptr;
+  }
+  int64_t nblocks = (total + PW_BLOCK - 1) / PW_BLOCK;
+  hipLaunchKernelGGL(k_gc_bucket_compact, dim3((uint32_t)nblocks),
+                     dim3(PW_BLOCK), 0, (hipStream_t)stream,
+                     (const long long*)base, (const uint32_t*)bucket_start,
+                     1u << bucket_bits, total, (const long long*)st_k0,
+                     (const long long*)st_k1, (const uint32_t*)st_first, sp,
+                     nacc, (long long*)out_k0, (long long*)out_k1,
+                     (long long*)out_first, op);
+  return (int)hipGetLastError();
+}
+
 extern "C" int pw_gc_emit(const void* k0_sorted, const void* k1_sorted,
                           const void* perm32, const void** contrib_ptrs,
                           int nacc, int64_t n, const void* block_csum,
