@@ -89,6 +89,13 @@ _PW_NO_HASHAGG = bool(_os.environ.get("PW_NO_HASHAGG"))
 #: (A/B)
 _PW_NO_GROUP_UPDATE = bool(_os.environ.get("PW_NO_GROUP_UPDATE"))
 
+#: fused consolidation (pw_consolidate_rows: row identity hash, prefix sort,
+#: diff sums and the drop of cancelled rows in one native call with one
+#: host read) for device batches of more than 2048 rows and at most 10
+#: columns — default ON; PW_NO_CONSOLIDATE_FUSED=1 forces the hash / sort /
+#: gather / seg-reduce chain (A/B)
+_PW_NO_CONSOLIDATE_FUSED = bool(_os.environ.get("PW_NO_CONSOLIDATE_FUSED"))
+
 #: returned by GroupReduceNode._group_update when the step is not its kind
 _NOT_FUSED = object()
 
@@ -140,12 +147,80 @@ def batch_vhash(batch: DeltaBatch) -> tuple[torch.Tensor, torch.Tensor]:
     return hashing.combine_value_hashes(parts)
 
 
+#: tensor dtypes whose value hash is hash128([tag, int64 payload])
+_RI_TAG_BY_DTYPE = {
+    dt.INT: hashing.TAG_INT,
+    dt.DATE_TIME_NAIVE: hashing.TAG_DT_NAIVE,
+    dt.DATE_TIME_UTC: hashing.TAG_DT_UTC,
+    dt.DURATION: hashing.TAG_DURATION,
+}
+
+
+def _row_ident_descs(batch: DeltaBatch) -> list[tuple]:
+    """Column descriptors of ops.consolidate_rows_gpu for a device batch:
+    int64 payloads, string codes and pointers are hashed inside the kernel,
+    every other column hands over its own value_hash()."""
+    from pathway_amd import ops
+
+    descs = []
+    for col in batch.columns.values():
+        if (
+            isinstance(col, TensorColumn)
+            and col.tensor.dtype == torch.int64
+            and col.tensor.dim() == 1
+            and col.tensor.is_cuda
+            and dt.unoptionalize(col.dtype) in _RI_TAG_BY_DTYPE
+        ):
+            tag = _RI_TAG_BY_DTYPE[dt.unoptionalize(col.dtype)]
+            descs.append((ops.RI_INT64_TAGGED, col.tensor, tag, col.mask))
+        elif isinstance(col, StringColumn) and col.codes.is_cuda:
+            lo_t, hi_t = col.pool.hash_tensors(col.codes.device)
+            descs.append((ops.RI_POOL_CODE, col.codes, lo_t, hi_t))
+        elif isinstance(col, PointerColumn) and col.pairs.is_cuda:
+            descs.append((ops.RI_POINTER, col.pairs, hashing.TAG_POINTER))
+        else:
+            lo, hi = col.value_hash()
+            descs.append((ops.RI_PRECOMPUTED, lo, hi))
+    return descs
+
+
+def _consolidate_fused(batch: DeltaBatch) -> DeltaBatch | None:
+    """consolidate_batch through ops.consolidate_rows_gpu.  The delivered
+    rows are those of the chain below, in its order, (c0, c1).  The chain
+    places rows by (c0, c1) and then separates neighbours by comparing
+    (key, vhash); this path groups by (c0, c1) itself.  The two differ only
+    if two different (key, vhash) rows collide in a 128-bit hash, and the
+    engine takes 128-bit hashes for identities everywhere (vhash is one).
+    Among equal rows the one that stands for the group may be another;
+    their values are equal by construction."""
+    from pathway_amd import ops
+
+    rows, wsum, keys = ops.consolidate_rows_gpu(
+        batch.keys, _row_ident_descs(batch), batch.diffs, gather_keys=True
+    )
+    if rows.shape[0] == 0:
+        return None
+    cols = {n: c.take(rows) for n, c in batch.columns.items()}
+    return DeltaBatch(keys, cols, wsum, batch.time)
+
+
 def consolidate_batch(batch: DeltaBatch) -> DeltaBatch | None:
     """Sort by (key, vhash), sum diffs, drop zeros (consolidation.rs)."""
     if batch is None or len(batch) == 0:
         return None
     if batch.consolidated:
         return batch
+    if len(batch) > 2048 and batch.keys.is_cuda:
+        from pathway_amd import ops
+
+        if (
+            not _PW_NO_CONSOLIDATE_FUSED
+            and len(batch.columns) <= ops.RI_MAX_COLS
+            and batch.diffs.dtype == torch.int64
+            and ops.lib_available()
+        ):
+            return _consolidate_fused(batch)
+        ops.consolidate_path_counts["chain"] += 1
     v0, v1 = batch_vhash(batch)
     words = [batch.keys[:, 0].contiguous(), batch.keys[:, 1].contiguous(), v0, v1]
     if len(batch) > 2048 and batch.keys.is_cuda:

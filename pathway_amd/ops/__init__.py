@@ -794,6 +794,217 @@ def group_combine_gpu(
     return out_k[0], out_k[1], out_first, [out_accs[a] for a in range(nacc)]
 
 
+#: column descriptor kinds of pw_row_ident / pw_consolidate_rows
+RI_INT64_TAGGED = 0
+RI_POOL_CODE = 1
+RI_POINTER = 2
+RI_PRECOMPUTED = 3
+#: widest batch the fused consolidation takes (20 hash words, as
+#: hash128_words_gpu)
+RI_MAX_COLS = 10
+
+#: which way consolidate_batch went for a device batch of more than 2048
+#: rows: the fused native call, that call redone after its prefix repair
+#: overflowed (counted in both), or the hash / sort / gather chain
+consolidate_path_counts = {"fused": 0, "overflow": 0, "chain": 0}
+
+
+def _ri_args(col_descs, n: int, dev):
+    """ctypes arrays for a list of column descriptors, and the tensors
+    they point into (to be kept alive until the launch is queued).
+
+    A descriptor is a tuple led by its kind:
+      (RI_INT64_TAGGED, payload int64 (n,), tag, mask bool (n,) or None)
+      (RI_POOL_CODE, codes int64 (n,), pool_lo, pool_hi)
+      (RI_POINTER, pairs int64 (n,2), tag)
+      (RI_PRECOMPUTED, lo int64 (n,), hi int64 (n,))"""
+    nc = len(col_descs)
+    assert nc <= RI_MAX_COLS
+    m = max(nc, 1)
+    kinds = (ctypes.c_int * m)()
+    pa = (ctypes.c_void_p * m)()
+    pb = (ctypes.c_void_p * m)()
+    pc = (ctypes.c_void_p * m)()
+    px = (ctypes.c_uint64 * m)()
+    keep = []
+
+    def dev_t(t, dtype, shape):
+        t = t.to(dev).contiguous()
+        assert t.dtype == dtype and tuple(t.shape) == shape, (t.dtype, t.shape)
+        keep.append(t)
+        return t.data_ptr()
+
+    for j, d in enumerate(col_descs):
+        kind = d[0]
+        kinds[j] = kind
+        if kind == RI_INT64_TAGGED:
+            pa[j] = dev_t(d[1], torch.int64, (n,))
+            px[j] = d[2] & (2**64 - 1)
+            if d[3] is not None:
+                pb[j] = dev_t(d[3], torch.bool, (n,))
+        elif kind == RI_POOL_CODE:
+            pa[j] = dev_t(d[1], torch.int64, (n,))
+            assert d[2].dtype == torch.int64 and d[2].shape == d[3].shape
+            pb[j] = dev_t(d[2], torch.int64, tuple(d[2].shape))
+            pc[j] = dev_t(d[3], torch.int64, tuple(d[3].shape))
+        elif kind == RI_POINTER:
+            pa[j] = dev_t(d[1], torch.int64, (n, 2))
+            px[j] = d[2] & (2**64 - 1)
+        elif kind == RI_PRECOMPUTED:
+            pa[j] = dev_t(d[1], torch.int64, (n,))
+            pb[j] = dev_t(d[2], torch.int64, (n,))
+        else:
+            raise ValueError(f"unknown row-ident column kind {kind}")
+    return (kinds, pa, pb, pc, px, ctypes.c_int(nc)), keep
+
+
+_none_hash_u64: tuple[int, int] | None = None
+
+
+def _none_hash():
+    global _none_hash_u64
+    if _none_hash_u64 is None:
+        from pathway_amd.internals.api import hash128, serialize_value
+
+        _none_hash_u64 = tuple(hash128(serialize_value(None)))
+    return _none_hash_u64
+
+
+def row_ident_gpu(keys: torch.Tensor, col_descs) -> torch.Tensor:
+    """(n,2) int64 row identities (c0, c1) of a batch, interleaved, in one
+    pass (pw_row_ident): bit-identical to the columns' value hashes,
+    combine_value_hashes and hash128_words([k0, k1, v0, v1]) in turn."""
+    lib = require_lib()
+    n = keys.shape[0]
+    assert keys.dtype == torch.int64 and keys.dim() == 2 and keys.shape[1] == 2
+    assert 1 <= n < 2**32
+    keys = keys.contiguous()
+    args, keep = _ri_args(col_descs, n, keys.device)
+    nlo, nhi = _none_hash()
+    ckeys = torch.empty((n, 2), dtype=torch.int64, device=keys.device)
+    lib.pw_row_ident.restype = ctypes.c_int
+    rc = lib.pw_row_ident(
+        ctypes.c_void_p(keys.data_ptr()),
+        ctypes.c_int64(n),
+        *args,
+        ctypes.c_uint64(nlo),
+        ctypes.c_uint64(nhi),
+        ctypes.c_void_p(ckeys.data_ptr()),
+        _stream_ptr(),
+    )
+    if rc != 0:
+        raise RuntimeError(f"pw_row_ident failed: hip error {rc}")
+    del keep
+    return ckeys
+
+
+def consolidate_rows_gpu(
+    keys: torch.Tensor,
+    col_descs,
+    diffs: torch.Tensor,
+    *,
+    prefix_bits: int = 32,
+    max_run: int = 2048,
+    max_dirty: int = 65536,
+    gather_keys: bool = False,
+) -> tuple:
+    """Consolidation of a device batch in one native call
+    (pw_consolidate_rows): (n,2) int64 keys, column descriptors (_ri_args)
+    and int64 diffs -> (rows, wsum), or with `gather_keys`
+    (rows, wsum, keys.index_select(0, rows)), the keys written by the
+    kernel that compacts the rows.
+
+    Ordering contract: the rows are grouped by their 128-bit identity
+    (c0, c1) = row_ident_gpu(keys, col_descs); `rows` holds the smallest
+    input row of every identity whose diffs do not sum to zero, identities
+    in signed lexicographic (c0, c1) order, and `wsum` the sums.  Grouping
+    by the identity itself, where the chain it replaces compared (key, value
+    hash) among neighbours, differs only if two 128-bit hashes collide,
+    which the engine rules out everywhere (the value hash is one).
+
+    One device-to-host read: survivors and the overflow word of the prefix
+    repair together.  On overflow (more than `max_run` rows share a 32-bit
+    prefix of c0 and differ, or more than `max_dirty` such runs) the
+    identities are grouped again by group_combine_gpu's 64-bit sort, with
+    further reads."""
+    lib = require_lib()
+    n = keys.shape[0]
+    dev = keys.device
+    assert keys.dtype == torch.int64 and keys.dim() == 2 and keys.shape[1] == 2
+    assert 2 <= n < 2**32
+    assert 1 <= prefix_bits <= 32 and 2 <= max_run <= 3072
+    assert 1 <= max_dirty < 2**32
+    keys = keys.contiguous()
+    diffs = diffs.contiguous()
+    assert diffs.dtype == torch.int64 and diffs.shape == (n,)
+    args, keep = _ri_args(col_descs, n, dev)
+    nlo, nhi = _none_hash()
+    nblocks = (n + 255) // 256
+    # one scratch allocation, in int64 words: ckeys (2n), k0_sorted,
+    # k1_sorted, first, sums (n each), block csum + ctl (nblocks + 4), then
+    # the 32-bit arrays perm32 (n), dirty_list (max_dirty), block_counts
+    h32 = lambda m: (m + 1) // 2
+    sizes = [2 * n, n, n, n, n, nblocks + 4, h32(n), h32(max_dirty), h32(nblocks)]
+    work = torch.empty(sum(sizes), dtype=torch.int64, device=dev)
+    ckeys_flat, k0s, k1s, first, sums, csum_ctl, perm32, dirty_list, block_counts = (
+        work.split(sizes)
+    )
+    ckeys = ckeys_flat.view(n, 2)
+    ctl = csum_ctl[nblocks:]
+    # the results are narrowed views of `out`: kept apart from the scratch,
+    # which a result then does not keep alive
+    out = torch.empty((4 if gather_keys else 2, n), dtype=torch.int64, device=dev)
+    out_rows, out_w = out[0], out[1]
+    out_keys = out[2:].view(n, 2) if gather_keys else None
+    temp, tbytes = _gc_temp(lib, n, True, dev)
+    lib.pw_consolidate_rows.restype = ctypes.c_int
+    rc = lib.pw_consolidate_rows(
+        ctypes.c_void_p(keys.data_ptr()),
+        ctypes.c_int64(n),
+        *args,
+        ctypes.c_uint64(nlo),
+        ctypes.c_uint64(nhi),
+        ctypes.c_void_p(diffs.data_ptr()),
+        ctypes.c_void_p(ckeys.data_ptr()),
+        ctypes.c_void_p(temp.data_ptr()),
+        ctypes.c_int64(tbytes),
+        ctypes.c_void_p(k0s.data_ptr()),
+        ctypes.c_void_p(k1s.data_ptr()),
+        ctypes.c_void_p(perm32.data_ptr()),
+        ctypes.c_int(prefix_bits),
+        ctypes.c_int64(max_run),
+        ctypes.c_int64(max_dirty),
+        ctypes.c_void_p(dirty_list.data_ptr()),
+        ctypes.c_void_p(ctl.data_ptr()),
+        ctypes.c_void_p(block_counts.data_ptr()),
+        ctypes.c_void_p(csum_ctl.data_ptr()),
+        ctypes.c_void_p(first.data_ptr()),
+        ctypes.c_void_p(sums.data_ptr()),
+        ctypes.c_void_p(out_rows.data_ptr()),
+        ctypes.c_void_p(out_w.data_ptr()),
+        ctypes.c_void_p(out_keys.data_ptr() if gather_keys else None),
+        _stream_ptr(),
+    )
+    if rc != 0:
+        raise RuntimeError(f"pw_consolidate_rows failed: hip error {rc}")
+    del keep
+    overflow, _dirty, total, _nseg = ctl.tolist()
+    consolidate_path_counts["fused"] += 1
+    if overflow:
+        consolidate_path_counts["overflow"] += 1
+        _uk0, _uk1, rows, (wsum,) = group_combine_gpu(
+            ckeys, [diffs], full_sort=True, bucket=False
+        )
+        nz = wsum.nonzero(as_tuple=True)[0]
+        rows, wsum = rows.index_select(0, nz), wsum.index_select(0, nz)
+        if gather_keys:
+            return rows, wsum, keys.index_select(0, rows)
+        return rows, wsum
+    if gather_keys:
+        return out_rows[:total], out_w[:total], out_keys[:total]
+    return out_rows[:total], out_w[:total]
+
+
 def partition_gpu(dest: torch.Tensor, world: int) -> tuple[torch.Tensor, torch.Tensor]:
     """Radix partition by destination rank: returns (perm, counts) with rows
     grouped by destination (exchange shuffle pack; pact.rs:56 analog)."""

@@ -3270,3 +3270,363 @@ extern "C" int pw_gc_emit(const void* k0_sorted, const void* k1_sorted,
                      (long long*)out_k1, (long long*)out_first, op);
   return (int)hipGetLastError();
 }
+
+// -------------------------------------------------- output consolidation --
+// consolidate_batch on the device, start to finish: rows of (key128,
+// columns..., diff) -> the rows that survive, with their summed diffs.
+//
+//   ident    k_row_ident: the 128-bit row identity (c0, c1) of every row,
+//            interleaved, in one pass (contract below)
+//   group    pw_gc_prefix_sort_count on the identities: prefix sort, gather,
+//            mark, repair, segment count (group combine, prefix sort, above)
+//   scan     k_cr_scan: inclusive scan of the block counts, in one block
+//   emit     k_cr_emit: k_gc_emit for one sum, without the key outputs
+//   nonzero  k_cr_nz<false>, k_cr_scan, k_cr_nz<true>: count, scan and
+//            compact the identities whose diffs do not sum to zero
+//
+// Every buffer is sized by n, so nothing on this path waits for a count:
+// the caller reads ctl once at the end and narrows rows / wsum to ctl[2].
+//
+// Ordering contract: rows[j] is the smallest input row of the j-th
+// surviving identity and wsum[j] its summed diff; identities ascend in
+// signed lexicographic (c0, c1) order, the order that a stable sort of c0
+// with word1 ties repaired gives.  Rows are grouped by (c0, c1) itself, not
+// by comparing (key, value hash) among neighbours: two different rows fall
+// together only where two 128-bit hashes collide, and the engine takes
+// 128-bit hashes for identities everywhere (the value hash is one).
+//
+// ctl (4 x uint64): [0] overflow of the prefix repair (the caller then
+// groups the identities with the 64-bit sort), [1] prefix runs listed,
+// [2] surviving identities, [3] identities.
+
+#define PW_RI_INT64_TAGGED 0
+#define PW_RI_POOL_CODE 1
+#define PW_RI_POINTER 2
+#define PW_RI_PRECOMPUTED 3
+#define PW_RI_MAX_COLS 10
+
+// One column of a row.  By kind:
+//   INT64_TAGGED  a = int64 payload, b = bool validity mask or null, x = tag
+//   POOL_CODE     a = int64 codes, b / c = the pool's lo / hi hash tables
+//   POINTER       a = (n,2) int64 pairs, x = the pointer tag
+//   PRECOMPUTED   a / b = the column's own lo / hi value hashes
+struct RiCol {
+  const void* a;
+  const void* b;
+  const void* c;
+  uint64_t x;
+  int kind;
+};
+
+struct RiCols {
+  RiCol c[PW_RI_MAX_COLS];
+};
+
+// Hash contract.  Per column the value hash (lo, hi) is
+//   INT64_TAGGED  hash128([tag, payload]) as k_value_hash; the None hash
+//                 where the mask is false
+//   POOL_CODE     (pool_lo[code], pool_hi[code]); the None hash for code < 0,
+//                 as k_pool_hash
+//   POINTER       hash128([tag, lo, hi])
+//   PRECOMPUTED   as given
+// then v = hash128([lo_0, hi_0, lo_1, hi_1, ...]) in column order, (0, 0)
+// without columns, and (c0, c1) = hash128([k0, k1, v0, v1]), written to
+// ckeys[2i], ckeys[2i + 1].  hash128 is (xxh64 seed LO, xxh64 seed HI) over
+// the words, as k_hash128_words: the result is bit-identical to the value
+// hashes, combine_value_hashes and hash128_words run one after the other.
+// Also clears sums[i], the accumulator k_cr_emit adds into.
+template <int NC>
+__global__ void k_row_ident(const uint64_t* __restrict__ keys, RiCols cols,
+                            uint64_t none_lo, uint64_t none_hi, int64_t n,
+                            uint64_t* __restrict__ ckeys,
+                            long long* __restrict__ sums) {
+  // one row per thread, no grid-stride loop: a loop makes the compiler
+  // keep all ten descriptors in scalar registers at once
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) {
+    uint64_t c[4];
+    c[0] = keys[2 * i];
+    c[1] = keys[2 * i + 1];
+    c[2] = 0;
+    c[3] = 0;
+    if (NC > 0) {
+      uint64_t w[NC > 0 ? 2 * NC : 2];
+#pragma unroll
+      for (int j = 0; j < NC; ++j) {
+        const RiCol& d = cols.c[j];
+        uint64_t lo, hi;
+        if (d.kind == PW_RI_INT64_TAGGED) {
+          uint64_t t[2] = {d.x, ((const uint64_t*)d.a)[i]};
+          lo = pw_xxh64_words<2>(t, PW_SEED_LO);
+          hi = pw_xxh64_words<2>(t, PW_SEED_HI);
+          if (d.b != nullptr && !((const uint8_t*)d.b)[i]) {
+            lo = none_lo;
+            hi = none_hi;
+          }
+        } else if (d.kind == PW_RI_POOL_CODE) {
+          int64_t code = ((const int64_t*)d.a)[i];
+          lo = none_lo;
+          hi = none_hi;
+          if (code >= 0) {
+            lo = ((const uint64_t*)d.b)[code];
+            hi = ((const uint64_t*)d.c)[code];
+          }
+        } else if (d.kind == PW_RI_POINTER) {
+          uint64_t t[3] = {d.x, ((const uint64_t*)d.a)[2 * i],
+                           ((const uint64_t*)d.a)[2 * i + 1]};
+          lo = pw_xxh64_words<3>(t, PW_SEED_LO);
+          hi = pw_xxh64_words<3>(t, PW_SEED_HI);
+        } else {
+          lo = ((const uint64_t*)d.a)[i];
+          hi = ((const uint64_t*)d.b)[i];
+        }
+        w[2 * j] = lo;
+        w[2 * j + 1] = hi;
+      }
+      c[2] = pw_xxh64_words<(NC > 0 ? 2 * NC : 2)>(w, PW_SEED_LO);
+      c[3] = pw_xxh64_words<(NC > 0 ? 2 * NC : 2)>(w, PW_SEED_HI);
+    }
+    ckeys[2 * i] = pw_xxh64_words<4>(c, PW_SEED_LO);
+    ckeys[2 * i + 1] = pw_xxh64_words<4>(c, PW_SEED_HI);
+    if (sums != nullptr) sums[i] = 0;
+  }
+}
+
+static int ri_fill(RiCols& cols, const int* kinds, const void** a,
+                   const void** b, const void** c, const uint64_t* x,
+                   int ncols) {
+  if (ncols < 0 || ncols > PW_RI_MAX_COLS) return 1;
+  for (int j = 0; j < PW_RI_MAX_COLS; ++j) {
+    RiCol& d = cols.c[j];
+    d.a = d.b = d.c = nullptr;
+    d.x = 0;
+    d.kind = PW_RI_PRECOMPUTED;
+    if (j >= ncols) continue;
+    if (kinds[j] < PW_RI_INT64_TAGGED || kinds[j] > PW_RI_PRECOMPUTED)
+      return 1;
+    d.kind = kinds[j];
+    d.a = a[j];
+    d.b = b[j];
+    d.c = c[j];
+    d.x = x[j];
+    if (d.a == nullptr) return 1;
+    if (d.kind == PW_RI_PRECOMPUTED && d.b == nullptr) return 1;
+    if (d.kind == PW_RI_POOL_CODE && (d.b == nullptr || d.c == nullptr))
+      return 1;
+  }
+  return 0;
+}
+
+static int ri_launch(const void* keys, const RiCols& cols, int ncols,
+                     uint64_t none_lo, uint64_t none_hi, int64_t n,
+                     void* ckeys, void* sums, hipStream_t s) {
+  dim3 grid((uint32_t)((n + PW_BLOCK - 1) / PW_BLOCK)), block(PW_BLOCK);
+#define CASE(NC)                                                          \
+  case NC:                                                                \
+    hipLaunchKernelGGL((k_row_ident<NC>), grid, block, 0, s,              \
+                       (const uint64_t*)keys, cols, none_lo, none_hi, n,  \
+                       (uint64_t*)ckeys, (long long*)sums);               \
+    break;
+  switch (ncols) {
+    CASE(0) CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7)
+    CASE(8) CASE(9) CASE(10)
+    default:
+      return 1;
+  }
+#undef CASE
+  return (int)hipGetLastError();
+}
+
+// keys: (n,2) int64 rows 16 B apart; ckeys: (n,2) int64 out.  kinds, a, b,
+// c, x: ncols entries each (see RiCol).
+extern "C" int pw_row_ident(const void* keys, int64_t n, const int* kinds,
+                            const void** a, const void** b, const void** c,
+                            const uint64_t* x, int ncols, uint64_t none_lo,
+                            uint64_t none_hi, void* ckeys, void* stream) {
+  if (n < 1 || n >= ((int64_t)1 << 32)) return 1;
+  RiCols cols;
+  if (ri_fill(cols, kinds, a, b, c, x, ncols)) return 1;
+  return ri_launch(keys, cols, ncols, none_lo, none_hi, n, ckeys, nullptr,
+                   (hipStream_t)stream);
+}
+
+// Inclusive scan of m int32 counts into int64, one block; the total also
+// goes to *total.
+#define PW_CR_SCAN_THREADS 1024
+
+__global__ __launch_bounds__(PW_CR_SCAN_THREADS) void k_cr_scan(
+    const int* __restrict__ counts, int64_t m, long long* __restrict__ csum,
+    unsigned long long* total) {
+  __shared__ long long wave_tot[PW_CR_SCAN_THREADS / 64];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  long long carry = 0;
+  for (int64_t t0 = 0; t0 < m; t0 += PW_CR_SCAN_THREADS) {
+    int64_t i = t0 + tid;
+    long long x = (i < m) ? (long long)counts[i] : 0;
+    for (int dlt = 1; dlt < 64; dlt <<= 1) {
+      long long y = __shfl_up(x, dlt, 64);
+      if (lane >= dlt) x += y;
+    }
+    if (lane == 63) wave_tot[wave] = x;
+    __syncthreads();
+    long long before = 0, all = 0;
+    for (int wv = 0; wv < PW_CR_SCAN_THREADS / 64; ++wv) {
+      long long wt = wave_tot[wv];
+      if (wv < wave) before += wt;
+      all += wt;
+    }
+    if (i < m) csum[i] = carry + before + x;
+    carry += all;
+    __syncthreads();
+  }
+  if (tid == 0) *total = (unsigned long long)carry;
+}
+
+// k_gc_emit for one sum and without the key outputs: the first (smallest)
+// input row of every (k0, k1) segment and the sum of contrib over its rows,
+// added into out_sum (cleared by k_row_ident).  block_csum: inclusive.
+__global__ void k_cr_emit(const long long* __restrict__ k0,
+                          const long long* __restrict__ k1,
+                          const uint32_t* __restrict__ perm32,
+                          const long long* __restrict__ contrib, int64_t n,
+                          const long long* __restrict__ block_csum,
+                          long long* out_first, long long* out_sum) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int lane = threadIdx.x & 63;
+  int flag = 0;
+  uint32_t row = 0;
+  if (i < n) {
+    row = perm32[i];
+    flag = (i == 0) || k0[i] != k0[i - 1] || k1[i] != k1[i - 1];
+  }
+  uint64_t ball = __ballot(flag);
+  int wave = threadIdx.x >> 6;
+  __shared__ int wave_tot[PW_BLOCK / 64];
+  if (lane == 0) wave_tot[wave] = __popcll(ball);
+  __syncthreads();
+  int wave_base = 0;
+  for (int j = 0; j < wave; ++j) wave_base += wave_tot[j];
+  uint64_t below = ball & ((lane == 0) ? 0ULL : ((1ULL << lane) - 1));
+  int local_excl = wave_base + __popcll(below);
+  long long base = blockIdx.x ? block_csum[blockIdx.x - 1] : 0;
+  long long sid = base + local_excl + flag - 1;
+  if (i < n && flag) out_first[sid] = (long long)row;
+  // padding lanes carry the sentinel -1, as in k_gc_emit
+  long long s = (i < n) ? sid : -1;
+  long long nxt = __shfl_down(s, 1, 64);
+  bool tail = (lane == 63) || (nxt != s);
+  long long v = (i < n) ? contrib[row] : 0;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    long long vv = __shfl_up(v, off, 64);
+    long long ss = __shfl_up(s, off, 64);
+    if (lane >= off && ss == s) v += vv;
+  }
+  if (s >= 0 && tail)
+    atomicAdd((unsigned long long*)&out_sum[s], (unsigned long long)v);
+}
+
+// Identities with a nonzero sum.  WRITE false: their number per block.
+// WRITE true: their first rows and sums, compacted in order, and with
+// out_keys given the (n,2) keys of those rows; block_csum is the inclusive
+// scan of the counts.  *nseg_p: the number of identities.
+template <bool WRITE>
+__global__ void k_cr_nz(const long long* __restrict__ first,
+                        const long long* __restrict__ sums, int64_t n,
+                        const unsigned long long* __restrict__ nseg_p,
+                        int* block_counts,
+                        const long long* __restrict__ block_csum,
+                        long long* __restrict__ out_rows,
+                        long long* __restrict__ out_w,
+                        const long long* __restrict__ keys,
+                        long long* __restrict__ out_keys) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t nseg = (int64_t)*nseg_p;
+  if (nseg > n) nseg = n;
+  int lane = threadIdx.x & 63;
+  int wave = threadIdx.x >> 6;
+  long long sm = (i < nseg) ? sums[i] : 0;
+  int flag = sm != 0;
+  uint64_t ball = __ballot(flag);
+  __shared__ int wave_tot[PW_BLOCK / 64];
+  if (lane == 0) wave_tot[wave] = __popcll(ball);
+  __syncthreads();
+  if (!WRITE) {
+    if (threadIdx.x == 0) {
+      int total = 0;
+      for (int j = 0; j < PW_BLOCK / 64; ++j) total += wave_tot[j];
+      block_counts[blockIdx.x] = total;
+    }
+  } else {
+    int wave_base = 0;
+    for (int j = 0; j < wave; ++j) wave_base += wave_tot[j];
+    uint64_t below = ball & ((lane == 0) ? 0ULL : ((1ULL << lane) - 1));
+    long long base = blockIdx.x ? block_csum[blockIdx.x - 1] : 0;
+    long long pos = base + wave_base + __popcll(below);
+    if (flag) {
+      long long row = first[i];
+      out_rows[pos] = row;
+      out_w[pos] = sm;
+      if (out_keys != nullptr) {
+        out_keys[2 * pos] = keys[2 * row];
+        out_keys[2 * pos + 1] = keys[2 * row + 1];
+      }
+    }
+  }
+}
+
+// The whole consolidation on the caller's stream, no host read inside.
+// keys (n,2) int64; column descriptors as pw_row_ident; diffs n int64.
+// Scratch: ckeys (n,2) int64, temp (pw_gc_temp_bytes_prefix(n)), k0_sorted,
+// k1_sorted, first, sums (n int64 each), perm32 (n uint32), dirty_list
+// (max_dirty uint32), block_counts (ceil(n/256) int32), csum (ceil(n/256)
+// int64).  Outputs: out_rows, out_w (n int64 each, ctl[2] of them valid),
+// out_keys (null, or (n,2) int64: keys[out_rows[j]] in row j) and ctl
+// (4 uint64, see above).  With ctl[0] set the outputs are void.
+extern "C" int pw_consolidate_rows(
+    const void* keys, int64_t n, const int* kinds, const void** a,
+    const void** b, const void** c, const uint64_t* x, int ncols,
+    uint64_t none_lo, uint64_t none_hi, const void* diffs, void* ckeys,
+    void* temp, int64_t temp_bytes, void* k0_sorted, void* k1_sorted,
+    void* perm32, int prefix_bits, int64_t max_run, int64_t max_dirty,
+    void* dirty_list, void* ctl, void* block_counts, void* csum, void* first,
+    void* sums, void* out_rows, void* out_w, void* out_keys, void* stream) {
+  if (n < 2 || n >= ((int64_t)1 << 32)) return 1;
+  RiCols cols;
+  if (ri_fill(cols, kinds, a, b, c, x, ncols)) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  int rc = ri_launch(keys, cols, ncols, none_lo, none_hi, n, ckeys, sums, s);
+  if (rc) return rc;
+  rc = pw_gc_prefix_sort_count(ckeys, n, temp, temp_bytes, k0_sorted,
+                               k1_sorted, perm32, prefix_bits, max_run,
+                               max_dirty, dirty_list, ctl, block_counts,
+                               stream);
+  if (rc) return rc;
+  unsigned long long* ctlw = (unsigned long long*)ctl;
+  int64_t nblocks = (n + PW_BLOCK - 1) / PW_BLOCK;
+  dim3 grid((uint32_t)nblocks), block(PW_BLOCK);
+  hipLaunchKernelGGL(k_cr_scan, dim3(1), dim3(PW_CR_SCAN_THREADS), 0, s,
+                     (const int*)block_counts, nblocks, (long long*)csum,
+                     ctlw + 3);
+  hipLaunchKernelGGL(k_cr_emit, grid, block, 0, s,
+                     (const long long*)k0_sorted, (const long long*)k1_sorted,
+                     (const uint32_t*)perm32, (const long long*)diffs, n,
+                     (const long long*)csum, (long long*)first,
+                     (long long*)sums);
+  hipLaunchKernelGGL((k_cr_nz<false>), grid, block, 0, s,
+                     (const long long*)first, (const long long*)sums, n,
+                     ctlw + 3, (int*)block_counts, (const long long*)csum,
+                     (long long*)out_rows, (long long*)out_w,
+                     (const long long*)keys, (long long*)out_keys);
+  hipLaunchKernelGGL(k_cr_scan, dim3(1), dim3(PW_CR_SCAN_THREADS), 0, s,
+                     (const int*)block_counts, nblocks, (long long*)csum,
+                     ctlw + 2);
+  hipLaunchKernelGGL((k_cr_nz<true>), grid, block, 0, s,
+                     (const long long*)first, (const long long*)sums, n,
+                     ctlw + 3, (int*)block_counts, (const long long*)csum,
+                     (long long*)out_rows, (long long*)out_w,
+                     (const long long*)keys, (long long*)out_keys);
+  return (int)hipGetLastError();
+}
