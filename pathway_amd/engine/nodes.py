@@ -89,6 +89,13 @@ _PW_NO_HASHAGG = bool(_os.environ.get("PW_NO_HASHAGG"))
 #: (A/B)
 _PW_NO_GROUP_UPDATE = bool(_os.environ.get("PW_NO_GROUP_UPDATE"))
 
+#: device path of the multiset reducers (pw_seg_select / pw_seg_distinct over
+#: the store's key ranges) for min / max / argmin / argmax / earliest /
+#: latest / any / unique / count_distinct on a GPU store — default ON;
+#: PW_NO_MULTISET_DEVICE=1 forces the torch scatter chain (min, max) and the
+#: per-group host loop (the rest) (A/B)
+_PW_NO_MULTISET_DEVICE = bool(_os.environ.get("PW_NO_MULTISET_DEVICE"))
+
 #: fused consolidation (pw_consolidate_rows: row identity hash, prefix sort,
 #: diff sums and the drop of cancelled rows in one native call with one
 #: host read) for device batches of more than 2048 rows and at most 10
@@ -1226,6 +1233,9 @@ class GroupReduceNode(Node):
                 cols[name] = column_from_pylist([None] * nq, dt.ANY, device)
             else:
                 cols[name] = _mask_missing(c.take(add_pos), add_found, device)
+        # the changed groups' row ranges in the multiset store, found once
+        # and shared by the reducers of this call
+        ranges: dict | None = None if _PW_NO_MULTISET_DEVICE else {}
         # additive reducer outputs
         w_cache: torch.Tensor | None = None
 
@@ -1249,7 +1259,9 @@ class GroupReduceNode(Node):
                     odt = dt.FLOAT if acc.dtype == torch.float64 else dt.INT
                     cols[out_name] = TensorColumn(acc, odt)
             elif spec.family == "multiset":
-                cols[out_name] = self._multiset_agg(out_name, spec, changed, nq, kwargs)
+                cols[out_name] = self._multiset_agg(
+                    out_name, spec, changed, nq, kwargs, ranges
+                )
         return presence, cols
 
 
@@ -1284,15 +1296,32 @@ class GroupReduceNode(Node):
         v = acc.index_select(0, pos)
         return v * found
 
-    def _multiset_agg(self, out_name, spec, changed, nq, rkw=None) -> Column:
+    def _multiset_agg(
+        self, out_name, spec, changed, nq, rkw=None, ranges=None
+    ) -> Column:
         device = self.device
         store = self.multiset_store
         arg0 = f"{out_name}__0"
         if store is None or len(store) == 0:
             proto_dt = dt.ANY
             return column_from_pylist([None] * nq, proto_dt, device)
-        lo, hi = store.key_range(changed)
-        rows, qidx = store.gather_ranges(lo, hi)
+        from pathway_amd import ops
+
+        # `ranges` is the cache of one _current_rows call; without one
+        # (PW_NO_MULTISET_DEVICE) every reducer looks its rows up itself
+        shared = ranges is not None
+        if ranges is None:
+            ranges = {}
+        if "lohi" not in ranges:
+            ranges["lohi"] = store.key_range(changed)
+        lo, hi = ranges["lohi"]
+        if shared and store.weights.is_cuda and nq > 0:
+            col = self._multiset_agg_device(out_name, spec, store, lo, hi)
+            if col is not None:
+                return col
+        if "rows" not in ranges:
+            ranges["rows"] = store.gather_ranges(lo, hi)
+        rows, qidx = ranges["rows"]
         col0 = store.columns[arg0]
         # GPU fast path for min/max over numeric columns
         if (
@@ -1300,15 +1329,14 @@ class GroupReduceNode(Node):
             and isinstance(col0, TensorColumn)
             and col0.mask is None
         ):
+            ops.multiset_path_counts["torch"] += 1
             vals = col0.tensor.index_select(0, rows)
             agg = spec.segment_agg(vals, qidx, nq)
-            out = agg
             if col0.tensor.dtype == torch.int64:
-                out = torch.where(
-                    torch.isfinite(agg), agg, torch.zeros_like(agg)
-                ).to(torch.int64)
-                return TensorColumn(out, dt.INT)
+                # _seg_min/_seg_max reduce int64 in int64 and zero empty groups
+                return TensorColumn(agg, dt.INT)
             return TensorColumn(torch.where(torch.isfinite(agg), agg, torch.zeros_like(agg)), dt.FLOAT)
+        ops.multiset_path_counts["host"] += 1
         # host path
         narg = spec.n_args if spec.n_args > 0 else 1
         arg_lists = []
@@ -1342,6 +1370,83 @@ class GroupReduceNode(Node):
         col, _ = _build_from_values(out_vals, device)
         return col
 
+    def _multiset_agg_device(self, out_name, spec, store, lo, hi) -> Column | None:
+        """One multiset reducer over the ranges [lo, hi) of a GPU store by
+        pw_seg_select / pw_seg_distinct, or None where the reducer or its
+        stored argument columns are not of the kind these kernels serve (the
+        caller then runs the host or torch path).
+
+        Rows of non-positive weight are skipped.  min/max/argmin/argmax pick
+        by arg0, earliest/latest by arg1, `any` takes the first row; ties go
+        to the first row in store order, as the host path's min()/max() do.
+        A NaN key beats every number for both directions (for min/max this
+        is the NaN propagation of the scatter chain; the host path's result
+        for the other reducers depends on the row order).  A group without
+        a positive row selects -1, clamped to row 0 here: its presence is
+        false and the row is never emitted.  The distinct reducers cost one
+        host read (any group given up; for `unique`, any group of more than
+        one value) and fall back as a whole when it is set."""
+        from pathway_amd import ops
+
+        name = spec.name
+        a0 = store.columns.get(f"{out_name}__0")
+        a1 = store.columns.get(f"{out_name}__1")
+        w = store.weights
+
+        def numeric(c):
+            return (
+                isinstance(c, TensorColumn)
+                and c.mask is None
+                and c.tensor.dim() == 1
+                and c.tensor.dtype in (torch.int64, torch.float64)
+            )
+
+        on_device = (TensorColumn, StringColumn, PointerColumn)
+        if name in ("count_distinct", "count_distinct_approximate", "unique"):
+            if isinstance(a0, StringColumn):
+                vals = a0.codes
+            elif numeric(a0) and a0.tensor.dtype == torch.int64:
+                vals = a0.tensor
+            else:
+                return None
+            count, first, status = ops.seg_distinct_gpu(lo, hi, w, vals.contiguous())
+            bad = status != 0
+            if name == "unique":
+                bad = bad | (count > 1)
+            if bool(bad.any()):
+                return None
+            ops.multiset_path_counts["distinct"] += 1
+            if name == "unique":
+                return a0.take(first.clamp_min(0))
+            return TensorColumn(count, dt.INT)
+        if name in ("min", "max", "argmin", "argmax"):
+            if not numeric(a0) or dt.unoptionalize(a0.dtype) not in (dt.INT, dt.FLOAT):
+                return None
+            mode = ops.SEG_MIN if name in ("min", "argmin") else ops.SEG_MAX
+            key = a0.tensor
+            if name in ("min", "max"):
+                odt = dt.INT if key.dtype == torch.int64 else dt.FLOAT
+                src = TensorColumn(key, odt)
+            elif isinstance(a1, PointerColumn):
+                src = a1
+            else:
+                return None
+        elif name in ("earliest", "latest"):
+            if not numeric(a1) or not isinstance(a0, on_device):
+                return None
+            mode = ops.SEG_MIN if name == "earliest" else ops.SEG_MAX
+            key, src = a1.tensor, a0
+        elif name == "any":
+            if not isinstance(a0, on_device):
+                return None
+            mode, key, src = ops.SEG_FIRST, None, a0
+        else:
+            return None
+        if key is not None:
+            key = key.contiguous()
+        sel = ops.seg_select_gpu(lo, hi, w, key, mode)
+        ops.multiset_path_counts["select"] += 1
+        return src.take(sel.clamp_min(0))
 
 def _build_from_values(vals, device):
     from pathway_amd.engine.column import infer_and_build_column

@@ -8,7 +8,11 @@ Two families, mirroring the reference:
     count_distinct/earliest/latest: state is the full weighted multiset of
     (group, value) rows; aggregates of changed groups are recomputed by
     segmented scans over the group's slice (reference ReducerImpl::combine,
-    reduce.rs:126-158).
+    reduce.rs:126-158).  On a GPU store min/max/argmin/argmax/earliest/
+    latest/any run through pw_seg_select and unique/count_distinct through
+    pw_seg_distinct (GroupReduceNode._multiset_agg_device); elsewhere
+    min/max take _seg_min/_seg_max (int64 reduced in int64, floats in
+    float64) and the rest the host_agg lambdas below.
 """
 
 from __future__ import annotations
@@ -98,16 +102,29 @@ _register(
 )
 
 
-def _seg_min(values: torch.Tensor, seg: torch.Tensor, nseg: int, argcol=None):
-    out = torch.full((nseg,), float("inf"), dtype=torch.float64, device=values.device)
-    out.scatter_reduce_(0, seg, values.to(torch.float64), reduce="amin", include_self=True)
+def _seg_extreme(values: torch.Tensor, seg: torch.Tensor, nseg: int, reduce: str):
+    if values.dtype == torch.int64:
+        # int64 stays int64: a float64 detour is wrong above 2**53.  Empty
+        # groups are told by a count, and read 0.
+        info = torch.iinfo(torch.int64)
+        init = info.max if reduce == "amin" else info.min
+        out = torch.full((nseg,), init, dtype=torch.int64, device=values.device)
+        out.scatter_reduce_(0, seg, values, reduce=reduce, include_self=True)
+        cnt = torch.zeros(nseg, dtype=torch.int64, device=values.device)
+        cnt.index_add_(0, seg, torch.ones_like(seg))
+        return torch.where(cnt > 0, out, torch.zeros_like(out))
+    init = float("inf") if reduce == "amin" else float("-inf")
+    out = torch.full((nseg,), init, dtype=torch.float64, device=values.device)
+    out.scatter_reduce_(0, seg, values.to(torch.float64), reduce=reduce, include_self=True)
     return out
+
+
+def _seg_min(values: torch.Tensor, seg: torch.Tensor, nseg: int, argcol=None):
+    return _seg_extreme(values, seg, nseg, "amin")
 
 
 def _seg_max(values: torch.Tensor, seg: torch.Tensor, nseg: int, argcol=None):
-    out = torch.full((nseg,), float("-inf"), dtype=torch.float64, device=values.device)
-    out.scatter_reduce_(0, seg, values.to(torch.float64), reduce="amax", include_self=True)
-    return out
+    return _seg_extreme(values, seg, nseg, "amax")
 
 
 def _multiset(name: str, seg_agg, host_agg, out_dtype, n_args: int = 1):

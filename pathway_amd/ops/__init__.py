@@ -231,6 +231,155 @@ def key_range_gpu(
     return lo, hi
 
 
+#: modes of seg_select_gpu
+SEG_FIRST = 0
+SEG_MIN = 1
+SEG_MAX = 2
+#: seg_select_gpu: a range of more rows than this is finished by the second
+#: launch, one 1024-thread workgroup per range (profiles/multiset_r09.md)
+SEG_SELECT_LONG = 4096
+#: seg_distinct_gpu: entries of the per-range LDS table; one pass fills
+#: GC_BUCKET_MAX_LOAD of it at the most and a range takes at most 64 passes
+SEG_DISTINCT_CAPACITY = 4096
+SEG_DISTINCT_MAX_PASSES = 64
+
+#: which path served each GroupReduceNode._multiset_agg call: the segmented
+#: select kernel, the segmented distinct kernel, the per-group host loop, or
+#: the torch scatter chain of min/max
+multiset_path_counts = {"select": 0, "distinct": 0, "host": 0, "torch": 0}
+
+
+def _check_ranges(lo: torch.Tensor, hi: torch.Tensor, weights: torch.Tensor):
+    for name, t in (("lo", lo), ("hi", hi), ("weights", weights)):
+        if t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous 1-D int64 tensor")
+        if not t.is_cuda or t.device != weights.device:
+            raise ValueError(f"{name} must be on the weights' GPU")
+    if lo.shape[0] != hi.shape[0]:
+        raise ValueError("lo and hi differ in length")
+
+
+def seg_select_gpu(
+    lo: torch.Tensor,
+    hi: torch.Tensor,
+    weights: torch.Tensor,
+    key: torch.Tensor | None,
+    mode: int,
+    long_rows: int | None = None,
+) -> torch.Tensor:
+    """The chosen store row of every range [lo[q], hi[q]), or -1 where the
+    range holds no row of positive weight (pw_seg_select; no host read).
+
+    Rows with weights[r] <= 0 are skipped in every mode.  SEG_FIRST takes
+    the smallest row index that is left and reads no key.  SEG_MIN / SEG_MAX
+    take the smallest / largest key; equal keys go to the smallest row
+    index.  int64 keys compare as int64.  float64 keys compare with < and >,
+    so -0.0 and 0.0 tie; a NaN key beats every number in both modes, and
+    NaNs tie by row index.  Ranges of more than `long_rows` rows (default
+    SEG_SELECT_LONG) are finished by a second launch."""
+    lib = require_lib()
+    _check_ranges(lo, hi, weights)
+    m = weights.shape[0]
+    if mode == SEG_FIRST:
+        if key is not None:
+            raise ValueError("SEG_FIRST reads no key")
+        kind, kptr = 0, None
+    elif mode in (SEG_MIN, SEG_MAX):
+        if key is None:
+            raise ValueError("SEG_MIN / SEG_MAX need a key column")
+        if key.dtype == torch.int64:
+            kind = 1
+        elif key.dtype == torch.float64:
+            kind = 2
+        else:
+            raise ValueError(f"key must be int64 or float64, not {key.dtype}")
+        if key.shape != (m,) or not key.is_contiguous() or key.device != weights.device:
+            raise ValueError("key must be a contiguous 1-D column of the store")
+        kptr = key.data_ptr()
+    else:
+        raise ValueError(f"unknown mode {mode}")
+    long_rows = SEG_SELECT_LONG if long_rows is None else int(long_rows)
+    if long_rows < 64:
+        raise ValueError("long_rows must be at least 64")
+    nq = lo.shape[0]
+    sel = torch.empty(nq, dtype=torch.int64, device=weights.device)
+    rc = lib.pw_seg_select(
+        ctypes.c_void_p(lo.data_ptr()),
+        ctypes.c_void_p(hi.data_ptr()),
+        ctypes.c_int64(nq),
+        ctypes.c_void_p(weights.data_ptr()),
+        ctypes.c_void_p(kptr),
+        ctypes.c_int(kind),
+        ctypes.c_int64(m),
+        ctypes.c_int(mode),
+        ctypes.c_int64(long_rows),
+        ctypes.c_void_p(sel.data_ptr()),
+        _stream_ptr(),
+    )
+    if rc != 0:
+        raise RuntimeError(f"pw_seg_select failed: error {rc}")
+    return sel
+
+
+def seg_distinct_gpu(
+    lo: torch.Tensor,
+    hi: torch.Tensor,
+    weights: torch.Tensor,
+    values: torch.Tensor,
+    table_capacity: int | None = None,
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(count, first, status) of every range [lo[q], hi[q]): the number of
+    distinct int64 `values` among its rows of positive weight, the first
+    such row (-1 if none), and status 0 = exact, 1 = given up with count 0
+    (pw_seg_distinct; no host read).
+
+    One workgroup per range with a set of `table_capacity` entries (default
+    SEG_DISTINCT_CAPACITY) in LDS.  A range of more distinct values than
+    GC_BUCKET_MAX_LOAD of the table is counted in a power-of-two number of
+    passes over disjoint hash classes, found by doubling; one that needs
+    more than SEG_DISTINCT_MAX_PASSES (any range of more than
+    SEG_DISTINCT_MAX_PASSES * GC_BUCKET_MAX_LOAD * table_capacity distinct
+    values does), or an insert that runs past GC_BUCKET_MAX_PROBE slots,
+    gives the range up, with first -1.  Every int64 is a value, -1
+    included."""
+    lib = require_lib()
+    _check_ranges(lo, hi, weights)
+    m = weights.shape[0]
+    if (
+        values.dtype != torch.int64
+        or values.shape != (m,)
+        or not values.is_contiguous()
+        or values.device != weights.device
+    ):
+        raise ValueError("values must be a contiguous 1-D int64 column of the store")
+    cap = SEG_DISTINCT_CAPACITY if table_capacity is None else int(table_capacity)
+    if cap < 64 or cap > 8192 or cap & (cap - 1):
+        raise ValueError("table_capacity must be a power of two in [64, 8192]")
+    nq = lo.shape[0]
+    dev = weights.device
+    count = torch.empty(nq, dtype=torch.int64, device=dev)
+    first = torch.empty(nq, dtype=torch.int64, device=dev)
+    status = torch.empty(nq, dtype=torch.int32, device=dev)
+    rc = lib.pw_seg_distinct(
+        ctypes.c_void_p(lo.data_ptr()),
+        ctypes.c_void_p(hi.data_ptr()),
+        ctypes.c_int64(nq),
+        ctypes.c_void_p(weights.data_ptr()),
+        ctypes.c_void_p(values.data_ptr()),
+        ctypes.c_int64(m),
+        ctypes.c_int64(cap),
+        ctypes.c_int64(int(GC_BUCKET_MAX_LOAD * cap)),
+        ctypes.c_int64(GC_BUCKET_MAX_PROBE),
+        ctypes.c_void_p(count.data_ptr()),
+        ctypes.c_void_p(first.data_ptr()),
+        ctypes.c_void_p(status.data_ptr()),
+        _stream_ptr(),
+    )
+    if rc != 0:
+        raise RuntimeError(f"pw_seg_distinct failed: error {rc}")
+    return count, first, status
+
+
 def pool_hash_gpu(
     codes: torch.Tensor,
     pool_lo: torch.Tensor,

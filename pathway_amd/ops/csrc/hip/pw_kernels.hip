@@ -3630,3 +3630,362 @@ extern "C" int pw_consolidate_rows(
                      (const long long*)keys, (long long*)out_keys);
   return (int)hipGetLastError();
 }
+
+// ------------------------------------------- multiset reducers: select --
+//
+// Segmented select behind min / max / argmin / argmax / earliest / latest /
+// any: the multiset store keeps a group's rows contiguous, pw_key_range
+// gives [lo, hi) per changed group, and these kernels pick one store row
+// per range (-1 where no row of the range has a positive weight):
+//
+//   FIRST  the smallest row index of positive weight; no key is read
+//   MIN    the smallest key, MAX the largest; equal keys go to the smallest
+//          row index, as Python's min()/max() over the store order do
+//
+// int64 keys compare as int64.  float64 keys compare with < and >, so -0.0
+// and 0.0 tie; a NaN beats every number in both modes and NaNs tie by row.
+//
+// k_seg_select_wave: one wave per range, lanes stride over the range, then
+// a 64-lane __shfl_down reduction of the (key, row) pair; waves take ranges
+// in a grid-stride loop.  A range longer than long_rows gets PW_SS_MARK and
+// k_seg_select_long finishes it: a 1024-thread workgroup per marked range,
+// a reduction per wave, then the 16 partials through LDS.  Every loop is
+// bounded by hi - lo, bounds are clamped to the store, nothing is read back.
+
+#define PW_SS_FIRST 0
+#define PW_SS_MIN 1
+#define PW_SS_MAX 2
+#define PW_SS_MARK (-2LL)
+#define PW_SS_LONG_THREADS 1024
+#define PW_SS_LONG_GRID 1024
+
+template <typename K>
+__device__ __forceinline__ bool ss_isnan(K) {
+  return false;
+}
+template <>
+__device__ __forceinline__ bool ss_isnan<double>(double k) {
+  return k != k;
+}
+
+// whether (ka, ra) is chosen over (kb, rb); a row of -1 is "none yet"
+template <typename K, int MODE>
+__device__ __forceinline__ bool ss_better(K ka, long long ra, K kb,
+                                          long long rb) {
+  if (ra < 0) return false;
+  if (rb < 0) return true;
+  if (MODE != PW_SS_FIRST) {
+    const bool an = ss_isnan(ka), bn = ss_isnan(kb);
+    if (an != bn) return an;
+    if (!an) {
+      if (MODE == PW_SS_MIN ? ka < kb : ka > kb) return true;
+      if (MODE == PW_SS_MIN ? kb < ka : kb > ka) return false;
+    }
+  }
+  return ra < rb;
+}
+
+template <typename K, int MODE>
+__device__ __forceinline__ void ss_scan(const long long* __restrict__ weights,
+                                        const K* __restrict__ key, int64_t lo,
+                                        int64_t hi, int64_t start,
+                                        int64_t step, K& bk, long long& br) {
+  for (int64_t r = lo + start; r < hi; r += step) {
+    if (weights[r] <= 0) continue;
+    if (MODE == PW_SS_FIRST) {
+      br = r;  // rows ascend: a lane's first positive row is its best
+      break;
+    }
+    const K k = key[r];
+    if (ss_better<K, MODE>(k, r, bk, br)) {
+      bk = k;
+      br = r;
+    }
+  }
+}
+
+// after this lane 0 holds the wave's best pair
+template <typename K, int MODE>
+__device__ __forceinline__ void ss_wave_reduce(K& bk, long long& br) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const K ok = __shfl_down(bk, off, 64);
+    const long long orow = __shfl_down(br, off, 64);
+    if (ss_better<K, MODE>(ok, orow, bk, br)) {
+      bk = ok;
+      br = orow;
+    }
+  }
+}
+
+__device__ __forceinline__ void ss_clamp(int64_t& lo, int64_t& hi, int64_t m) {
+  if (lo < 0) lo = 0;
+  if (hi > m) hi = m;
+  if (hi < lo) hi = lo;
+}
+
+template <typename K, int MODE>
+__global__ __launch_bounds__(PW_BLOCK) void k_seg_select_wave(
+    const long long* __restrict__ lo_in, const long long* __restrict__ hi_in,
+    int64_t nq, const long long* __restrict__ weights,
+    const K* __restrict__ key, int64_t m, int64_t long_rows,
+    long long* __restrict__ sel) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * PW_BLOCK + threadIdx.x) >> 6;
+  const int64_t nwaves = ((int64_t)gridDim.x * PW_BLOCK) >> 6;
+  for (int64_t q = wave; q < nq; q += nwaves) {
+    int64_t lo = lo_in[q], hi = hi_in[q];
+    ss_clamp(lo, hi, m);
+    if (hi - lo > long_rows) {
+      if (lane == 0) sel[q] = PW_SS_MARK;
+      continue;
+    }
+    K bk = K(0);
+    long long br = -1;
+    ss_scan<K, MODE>(weights, key, lo, hi, lane, 64, bk, br);
+    ss_wave_reduce<K, MODE>(bk, br);
+    if (lane == 0) sel[q] = br;
+  }
+}
+
+template <typename K, int MODE>
+__global__ __launch_bounds__(PW_SS_LONG_THREADS) void k_seg_select_long(
+    const long long* __restrict__ lo_in, const long long* __restrict__ hi_in,
+    int64_t nq, const long long* __restrict__ weights,
+    const K* __restrict__ key, int64_t m, long long* sel) {
+  __shared__ K pk[PW_SS_LONG_THREADS / 64];
+  __shared__ long long pr[PW_SS_LONG_THREADS / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  for (int64_t q = blockIdx.x; q < nq; q += gridDim.x) {
+    // every thread reads the marker before the barriers below, thread 0
+    // overwrites it after them
+    if (sel[q] != PW_SS_MARK) continue;
+    int64_t lo = lo_in[q], hi = hi_in[q];
+    ss_clamp(lo, hi, m);
+    K bk = K(0);
+    long long br = -1;
+    ss_scan<K, MODE>(weights, key, lo, hi, tid, PW_SS_LONG_THREADS, bk, br);
+    ss_wave_reduce<K, MODE>(bk, br);
+    if (lane == 0) {
+      pk[wv] = bk;
+      pr[wv] = br;
+    }
+    __syncthreads();
+    if (wv == 0) {
+      const bool has = lane < PW_SS_LONG_THREADS / 64;
+      bk = has ? pk[lane] : K(0);
+      br = has ? pr[lane] : -1;
+      ss_wave_reduce<K, MODE>(bk, br);
+      if (lane == 0) sel[q] = br;
+    }
+    __syncthreads();
+  }
+}
+
+template <typename K, int MODE>
+static int ss_launch(const void* lo, const void* hi, int64_t nq,
+                     const void* weights, const void* key, int64_t m,
+                     int64_t long_rows, void* sel, hipStream_t s) {
+  // four waves a block; the grid-stride loop takes the rest
+  int64_t g = (nq + 3) / 4;
+  if (g > PW_MAX_GRID) g = PW_MAX_GRID;
+  hipLaunchKernelGGL((k_seg_select_wave<K, MODE>), dim3((uint32_t)g),
+                     dim3(PW_BLOCK), 0, s, (const long long*)lo,
+                     (const long long*)hi, nq, (const long long*)weights,
+                     (const K*)key, m, long_rows, (long long*)sel);
+  if (m > long_rows) {  // else no range can carry the marker
+    int64_t gl = nq < PW_SS_LONG_GRID ? nq : PW_SS_LONG_GRID;
+    hipLaunchKernelGGL((k_seg_select_long<K, MODE>), dim3((uint32_t)gl),
+                       dim3(PW_SS_LONG_THREADS), 0, s, (const long long*)lo,
+                       (const long long*)hi, nq, (const long long*)weights,
+                       (const K*)key, m, (long long*)sel);
+  }
+  return (int)hipGetLastError();
+}
+
+// lo, hi, sel: nq int64; weights: m int64; key: m int64 (key_kind 1) or m
+// float64 (key_kind 2), unused with mode FIRST; long_rows >= 64.
+extern "C" int pw_seg_select(const void* lo, const void* hi, int64_t nq,
+                             const void* weights, const void* key,
+                             int key_kind, int64_t m, int mode,
+                             int64_t long_rows, void* sel, void* stream) {
+  if (nq < 0 || m < 0 || long_rows < 64) return 1;
+  if (nq == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (mode == PW_SS_FIRST)
+    return ss_launch<long long, PW_SS_FIRST>(lo, hi, nq, weights, nullptr, m,
+                                             long_rows, sel, s);
+  if (mode != PW_SS_MIN && mode != PW_SS_MAX) return 1;
+  if (key == nullptr && m > 0) return 1;
+  const bool mn = mode == PW_SS_MIN;
+  if (key_kind == 1)
+    return mn ? ss_launch<long long, PW_SS_MIN>(lo, hi, nq, weights, key, m,
+                                                long_rows, sel, s)
+              : ss_launch<long long, PW_SS_MAX>(lo, hi, nq, weights, key, m,
+                                                long_rows, sel, s);
+  if (key_kind == 2)
+    return mn ? ss_launch<double, PW_SS_MIN>(lo, hi, nq, weights, key, m,
+                                             long_rows, sel, s)
+              : ss_launch<double, PW_SS_MAX>(lo, hi, nq, weights, key, m,
+                                             long_rows, sel, s);
+  return 1;
+}
+
+// ----------------------------------------- multiset reducers: distinct --
+//
+// Number of distinct 64-bit values among the rows of positive weight of
+// every range (count_distinct, and unique through count == 1), with the
+// range's first such row.  One workgroup per range, ranges in a grid-stride
+// loop.  The set is an open-addressing table of row offsets in LDS, in the
+// idiom of k_gc_bucket_agg: a slot is claimed by a CAS of the row's offset
+// over EMPTY, and a slot's value is read from the row that owns it, so no
+// value needs a sentinel and no thread waits on another.
+//
+// One pass may claim max_hold slots (the table at its load limit).  A range
+// with more distinct values than that is counted in P passes, P a power of
+// two: pass p inserts the values whose mixed hash has p in its top bits,
+// the slot comes from the low bits, and the table is cleared between
+// passes.  P is found by doubling: the count starts at one pass, and a pass
+// that would claim slot max_hold + 1 ends the attempt at once and starts
+// the next with 2 P, so a long range of few values costs one pass and the
+// attempts that fail cost about max_hold claims each.  A range that
+// overflows a pass at PW_SD_MAX_PASSES passes (any range of more than
+// PW_SD_MAX_PASSES * max_hold distinct values does), or an insert that runs
+// out of max_probe probes, gives the range up: status 1, count 0, first -1.
+
+#define PW_SD_THREADS 1024
+#define PW_SD_GRID 1024
+#define PW_SD_EMPTY 0xFFFFFFFFu
+#define PW_SD_MAX_PASSES 64
+#define PW_SD_MAX_CAPACITY 8192  // 32 KB of LDS
+
+__device__ __forceinline__ uint64_t sd_mix(uint64_t x) {
+  x ^= x >> 33;
+  x *= 0xFF51AFD7ED558CCDULL;
+  x ^= x >> 33;
+  x *= 0xC4CEB9FE1A85EC53ULL;
+  x ^= x >> 33;
+  return x;
+}
+
+__global__ __launch_bounds__(PW_SD_THREADS) void k_seg_distinct(
+    const long long* __restrict__ lo_in, const long long* __restrict__ hi_in,
+    int64_t nq, const long long* __restrict__ weights,
+    const long long* __restrict__ values, int64_t m, uint32_t cap,
+    uint32_t max_hold, uint32_t max_probe, long long* __restrict__ count,
+    long long* __restrict__ first, int* __restrict__ status) {
+  extern __shared__ uint32_t sd_tab[];  // [cap] row offsets into the range
+  // s_stop: 1 = a pass is over its share (next attempt), 2 = out of probes
+  __shared__ uint32_t s_claims, s_first, s_stop;
+  const uint32_t tid = threadIdx.x;
+  for (int64_t q = blockIdx.x; q < nq; q += gridDim.x) {
+    int64_t lo = lo_in[q], hi = hi_in[q];
+    ss_clamp(lo, hi, m);
+    const int64_t len = hi - lo;
+    if (len >= (int64_t)PW_SD_EMPTY) {  // offsets are 32 bits; uniform
+      if (tid == 0) count[q] = 0, first[q] = -1, status[q] = 1;
+      continue;
+    }
+    const uint32_t rows = (uint32_t)len;
+    // a short range clears and probes only the table it needs
+    uint32_t tcap = cap;
+    if (rows <= max_hold) {
+      tcap = 64;
+      while (tcap < 2 * rows && tcap < cap) tcap <<= 1;
+    }
+    const uint32_t mask = tcap - 1;
+    const uint32_t probes = max_probe < tcap ? max_probe : tcap;
+    if (tid == 0) s_first = PW_SD_EMPTY;
+    uint32_t myfirst = PW_SD_EMPTY;
+    uint32_t total = 0, stop = 0;
+    int lg_passes = 0;
+    for (;;) {  // attempts: 1, 2, 4, ... PW_SD_MAX_PASSES passes
+      total = 0;
+      for (uint32_t p = 0; p < (1u << lg_passes); ++p) {
+        if (tid == 0) s_claims = 0, s_stop = 0;
+        for (uint32_t sl = tid; sl < tcap; sl += PW_SD_THREADS)
+          sd_tab[sl] = PW_SD_EMPTY;
+        __syncthreads();
+        for (uint32_t i = tid; i < rows; i += PW_SD_THREADS) {
+          if (__hip_atomic_load(&s_stop, __ATOMIC_RELAXED,
+                                __HIP_MEMORY_SCOPE_WORKGROUP))
+            break;
+          if (weights[lo + i] <= 0) continue;
+          if (i < myfirst) myfirst = i;
+          const long long v = values[lo + i];
+          const uint64_t h = sd_mix((uint64_t)v);
+          if (lg_passes && (uint32_t)(h >> (64 - lg_passes)) != p) continue;
+          uint32_t slot = (uint32_t)h & mask;
+          bool done = false;
+          for (uint32_t t = 0; t < probes; ++t) {
+            uint32_t cur = __hip_atomic_load(&sd_tab[slot], __ATOMIC_RELAXED,
+                                             __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (cur == PW_SD_EMPTY) {
+              cur = atomicCAS(&sd_tab[slot], PW_SD_EMPTY, i);
+              if (cur == PW_SD_EMPTY) {  // claimed: a new value
+                if (atomicAdd(&s_claims, 1u) >= max_hold) atomicMax(&s_stop, 1u);
+                done = true;
+                break;
+              }
+            }
+            if (values[lo + cur] == v) {  // cur < rows: some row's own offset
+              done = true;
+              break;
+            }
+            slot = (slot + 1) & mask;
+          }
+          if (!done) atomicMax(&s_stop, 2u);
+        }
+        __syncthreads();
+        stop = s_stop;
+        total += s_claims;
+        __syncthreads();  // all have read before thread 0 resets
+        if (stop) break;
+      }
+      if (stop != 1 || (1 << lg_passes) >= PW_SD_MAX_PASSES) break;
+      ++lg_passes;
+    }
+    // the attempt that held visited every row in its pass 0
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const uint32_t of = __shfl_down(myfirst, off, 64);
+      myfirst = of < myfirst ? of : myfirst;
+    }
+    if ((tid & 63) == 0 && myfirst != PW_SD_EMPTY) atomicMin(&s_first, myfirst);
+    __syncthreads();
+    if (tid == 0) {
+      const bool ok = stop == 0 && s_first != PW_SD_EMPTY;
+      count[q] = stop ? 0 : (long long)total;
+      first[q] = ok ? lo + (int64_t)s_first : -1;
+      status[q] = stop ? 1 : 0;
+    }
+    __syncthreads();
+  }
+}
+
+// lo, hi, count, first: nq int64; status: nq int32; weights, values: m
+// int64.  table_capacity: a power of two in [64, PW_SD_MAX_CAPACITY];
+// max_hold in [1, table_capacity): rows one pass is sized for.
+extern "C" int pw_seg_distinct(const void* lo, const void* hi, int64_t nq,
+                               const void* weights, const void* values,
+                               int64_t m, int64_t table_capacity,
+                               int64_t max_hold, int64_t max_probe,
+                               void* count, void* first, void* status,
+                               void* stream) {
+  if (nq < 0 || m < 0) return 1;
+  if (table_capacity < 64 || table_capacity > PW_SD_MAX_CAPACITY ||
+      (table_capacity & (table_capacity - 1)))
+    return 1;
+  if (max_hold < 1 || max_hold >= table_capacity || max_probe < 1) return 1;
+  if (nq == 0) return 0;
+  if (max_probe > table_capacity) max_probe = table_capacity;
+  int64_t g = nq < PW_SD_GRID ? nq : PW_SD_GRID;
+  hipLaunchKernelGGL(k_seg_distinct, dim3((uint32_t)g), dim3(PW_SD_THREADS),
+                     (size_t)table_capacity * sizeof(uint32_t),
+                     (hipStream_t)stream, (const long long*)lo,
+                     (const long long*)hi, nq, (const long long*)weights,
+                     (const long long*)values, m, (uint32_t)table_capacity,
+                     (uint32_t)max_hold, (uint32_t)max_probe,
+                     (long long*)count, (long long*)first, (int*)status);
+  return (int)hipGetLastError();
+}
