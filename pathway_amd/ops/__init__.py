@@ -610,6 +610,19 @@ class _GcPathCounts(dict):
 
 gc_path_counts = _GcPathCounts({"prefix": 0, "fallback": 0, "full": 0})
 
+#: PW_NO_GC_PARTITION=1 keeps the bucket path on its sort-and-gather layout
+_PW_NO_GC_PARTITION = bool(os.environ.get("PW_NO_GC_PARTITION"))
+#: PW_GC_PART_DIRECT=1 scatters the partition from registers instead of
+#: ordering it in LDS first (A/B runs, profiles/wordcount_r10.md)
+_PW_GC_PART_DIRECT = bool(os.environ.get("PW_GC_PART_DIRECT"))
+#: how a bucket-path call that held laid its rows out: moved into bucket
+#: order by the partition kernels, or sorted by bucket and gathered
+gc_bucket_layout_counts = {"partition": 0, "gather": 0}
+#: rows per workgroup of the partition kernels (PW_GC_PT_TILE)
+GC_PART_TILE = 8192
+#: the partition layout serves at most this many bucket bits
+GC_PART_MAX_BITS = 8
+
 #: whether a group_combine_gpu call that does not say `bucket=` tries the
 #: bucket path; the groupby node sets it around its call (gc_bucket_scope)
 _gc_bucket_scope = False
@@ -700,21 +713,95 @@ def _group_combine_two_sorts(keys_n2, contribs):
     return uk0, uk1, perm.index_select(0, first_sorted), accs
 
 
+def _gc_part_hist_entries(lib, n: int, bucket_bits: int) -> int:
+    fn = lib.pw_gc_part_hist_entries
+    fn.restype = ctypes.c_int64
+    entries = int(fn(ctypes.c_int64(n), ctypes.c_int(bucket_bits)))
+    if entries <= 0:
+        raise RuntimeError("pw_gc_part_hist_entries failed")
+    tile = lib.pw_gc_part_tile
+    tile.restype = ctypes.c_int64
+    assert int(tile()) == GC_PART_TILE
+    return entries
+
+
+def _gc_aligned_keys(keys_n2: torch.Tensor) -> torch.Tensor:
+    """The partition kernels read a key as one 128-bit load."""
+    return keys_n2.clone() if keys_n2.data_ptr() % 16 else keys_n2
+
+
+def gc_partition_gpu(
+    keys_n2: torch.Tensor, contribs: Sequence[torch.Tensor], bucket_bits: int
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, list]:
+    """The partition step of the bucket path on its own, for tests
+    (k_gc_part_count, _scan, _scatter): (bucket_start (2^bits + 1) int64,
+    part_keys (n,2), part_row (n) int64, part_accs), the rows grouped by
+    bucket in signed key order, in no particular order inside a bucket."""
+    lib = require_lib()
+    n = keys_n2.shape[0]
+    dev = keys_n2.device
+    nacc = len(contribs)
+    assert keys_n2.dim() == 2 and keys_n2.shape[1] == 2
+    assert keys_n2.dtype == torch.int64
+    assert 2 <= n < 2**32 - 1 and nacc <= 8 and 1 <= bucket_bits <= 8
+    if keys_n2.stride() != (2, 1):
+        keys_n2 = keys_n2.contiguous()
+    keys_n2 = _gc_aligned_keys(keys_n2)
+    contribs = [c.contiguous() for c in contribs]
+    assert all(c.dtype == torch.int64 and c.shape == (n,) for c in contribs)
+    nb = 1 << bucket_bits
+    hist = _gc_part_hist_entries(lib, n, bucket_bits)
+    part64 = torch.empty((2 + nacc, n), dtype=torch.int64, device=dev)
+    # block_hist, part_row, bucket_start (uint32 bits)
+    scratch32 = torch.empty(hist + n + nb + 1, dtype=torch.int32, device=dev)
+    ctl = torch.empty(2, dtype=torch.int64, device=dev)
+    carr = (ctypes.c_void_p * max(nacc, 1))(
+        *[ctypes.c_void_p(c.data_ptr()) for c in contribs]
+    )
+    parr = (ctypes.c_void_p * max(nacc, 1))(
+        *[ctypes.c_void_p(part64[2 + a].data_ptr()) for a in range(nacc)]
+    )
+    rc = lib.pw_gc_partition(
+        ctypes.c_void_p(keys_n2.data_ptr()),
+        ctypes.c_int64(n),
+        ctypes.c_int(bucket_bits),
+        carr,
+        ctypes.c_int(nacc),
+        ctypes.c_void_p(scratch32.data_ptr()),
+        ctypes.c_void_p(part64.data_ptr()),
+        ctypes.c_void_p(scratch32[hist:].data_ptr()),
+        parr,
+        ctypes.c_void_p(scratch32[hist + n :].data_ptr()),
+        ctypes.c_void_p(ctl.data_ptr()),
+        ctypes.c_int(int(_PW_GC_PART_DIRECT)),
+        _stream_ptr(),
+    )
+    if rc != 0:
+        raise RuntimeError(f"pw_gc_partition failed: hip error {rc}")
+    u32 = lambda t: t.to(torch.int64) & 0xFFFFFFFF  # noqa: E731
+    return (
+        u32(scratch32[hist + n :]),
+        part64[:2].reshape(n, 2),
+        u32(scratch32[hist : hist + n]),
+        [part64[2 + a] for a in range(nacc)],
+    )
+
+
 def _group_combine_bucket(
-    lib, keys_n2, contribs, bucket_bits, table_capacity, max_bucket_rows
+    lib, keys_n2, contribs, bucket_bits, table_capacity, max_bucket_rows,
+    partition=False,
 ):
     """group_combine_gpu's bucket path (pw_gc_bucket_*).  Returns the
     result, or None when a bucket overflowed its table, its row limit or
-    the probe bound.  One host read: total unique keys + overflow word."""
+    the probe bound.  One host read: total unique keys + overflow word.
+    `partition`: the rows are moved into bucket order (pw_gc_bucket_part_agg,
+    bucket_bits <= 8) instead of being sorted by bucket and gathered."""
     n = keys_n2.shape[0]
     dev = keys_n2.device
     nacc = len(contribs)
     nb = 1 << bucket_bits
     max_distinct = max(1, int(GC_BUCKET_MAX_LOAD * table_capacity))
     stream = _stream_ptr()
-    temp, tbytes = _gc_temp(lib, n, True, dev)
-    scratch32 = torch.empty((3, n), dtype=torch.int32, device=dev)  # uint32 bits
-    staged = torch.empty((2 + max(nacc, 1), n), dtype=torch.int64, device=dev)
     # bucket_start (nb+1), bucket_uniques (nb)
     bounds = torch.empty(2 * nb + 1, dtype=torch.int32, device=dev)
     # base (nb+1), then total and overflow word for one read
@@ -722,35 +809,83 @@ def _group_combine_bucket(
     carr = (ctypes.c_void_p * max(nacc, 1))(
         *[ctypes.c_void_p(c.data_ptr()) for c in contribs]
     )
+    if partition:
+        keys_n2 = _gc_aligned_keys(keys_n2)
+        hist = _gc_part_hist_entries(lib, n, bucket_bits)
+        # block_hist, part_row, st_first (uint32 bits)
+        scratch32 = torch.empty(hist + 2 * n, dtype=torch.int32, device=dev)
+        st_first = scratch32[hist + n :]
+        # part_keys (n,2), nacc partitioned columns, then the staging rows
+        staged = torch.empty(
+            (2 + nacc + 2 + max(nacc, 1), n), dtype=torch.int64, device=dev
+        )
+        st0 = 2 + nacc
+        parr = (ctypes.c_void_p * max(nacc, 1))(
+            *[ctypes.c_void_p(staged[2 + a].data_ptr()) for a in range(nacc)]
+        )
+    else:
+        temp, tbytes = _gc_temp(lib, n, True, dev)
+        scratch32 = torch.empty((3, n), dtype=torch.int32, device=dev)  # uint32 bits
+        st_first = scratch32[2]
+        staged = torch.empty((2 + max(nacc, 1), n), dtype=torch.int64, device=dev)
+        st0 = 0
     sarr = (ctypes.c_void_p * max(nacc, 1))(
-        *[ctypes.c_void_p(staged[2 + a].data_ptr()) for a in range(nacc)]
+        *[ctypes.c_void_p(staged[st0 + 2 + a].data_ptr()) for a in range(nacc)]
     )
-    rc = lib.pw_gc_bucket_agg(
-        ctypes.c_void_p(keys_n2.data_ptr()),
-        ctypes.c_int64(n),
-        ctypes.c_void_p(temp.data_ptr()),
-        ctypes.c_int64(tbytes),
-        ctypes.c_void_p(scratch32[0].data_ptr()),
-        ctypes.c_void_p(scratch32[1].data_ptr()),
-        ctypes.c_int(bucket_bits),
-        ctypes.c_int64(table_capacity),
-        ctypes.c_int64(max_distinct),
-        ctypes.c_int64(max_bucket_rows),
-        ctypes.c_int64(min(table_capacity, GC_BUCKET_MAX_PROBE)),
-        carr,
-        ctypes.c_int(nacc),
-        ctypes.c_void_p(bounds.data_ptr()),
-        ctypes.c_void_p(bounds[nb + 1 :].data_ptr()),
-        ctypes.c_void_p(base_ctl.data_ptr()),
-        ctypes.c_void_p(staged[0].data_ptr()),
-        ctypes.c_void_p(staged[1].data_ptr()),
-        ctypes.c_void_p(scratch32[2].data_ptr()),
-        sarr,
-        ctypes.c_void_p(base_ctl[nb + 1 :].data_ptr()),
-        stream,
-    )
+    if partition:
+        rc = lib.pw_gc_bucket_part_agg(
+            ctypes.c_void_p(keys_n2.data_ptr()),
+            ctypes.c_int64(n),
+            ctypes.c_int(bucket_bits),
+            ctypes.c_int64(table_capacity),
+            ctypes.c_int64(max_distinct),
+            ctypes.c_int64(max_bucket_rows),
+            ctypes.c_int64(min(table_capacity, GC_BUCKET_MAX_PROBE)),
+            carr,
+            ctypes.c_int(nacc),
+            ctypes.c_void_p(scratch32.data_ptr()),
+            ctypes.c_void_p(staged.data_ptr()),
+            ctypes.c_void_p(scratch32[hist:].data_ptr()),
+            parr,
+            ctypes.c_void_p(bounds.data_ptr()),
+            ctypes.c_void_p(bounds[nb + 1 :].data_ptr()),
+            ctypes.c_void_p(base_ctl.data_ptr()),
+            ctypes.c_void_p(staged[st0].data_ptr()),
+            ctypes.c_void_p(staged[st0 + 1].data_ptr()),
+            ctypes.c_void_p(st_first.data_ptr()),
+            sarr,
+            ctypes.c_void_p(base_ctl[nb + 1 :].data_ptr()),
+            ctypes.c_int(int(_PW_GC_PART_DIRECT)),
+            stream,
+        )
+    else:
+        rc = lib.pw_gc_bucket_agg(
+            ctypes.c_void_p(keys_n2.data_ptr()),
+            ctypes.c_int64(n),
+            ctypes.c_void_p(temp.data_ptr()),
+            ctypes.c_int64(tbytes),
+            ctypes.c_void_p(scratch32[0].data_ptr()),
+            ctypes.c_void_p(scratch32[1].data_ptr()),
+            ctypes.c_int(bucket_bits),
+            ctypes.c_int64(table_capacity),
+            ctypes.c_int64(max_distinct),
+            ctypes.c_int64(max_bucket_rows),
+            ctypes.c_int64(min(table_capacity, GC_BUCKET_MAX_PROBE)),
+            carr,
+            ctypes.c_int(nacc),
+            ctypes.c_void_p(bounds.data_ptr()),
+            ctypes.c_void_p(bounds[nb + 1 :].data_ptr()),
+            ctypes.c_void_p(base_ctl.data_ptr()),
+            ctypes.c_void_p(staged[0].data_ptr()),
+            ctypes.c_void_p(staged[1].data_ptr()),
+            ctypes.c_void_p(st_first.data_ptr()),
+            sarr,
+            ctypes.c_void_p(base_ctl[nb + 1 :].data_ptr()),
+            stream,
+        )
     if rc != 0:
-        raise RuntimeError(f"pw_gc_bucket_agg failed: hip error {rc}")
+        fn = "pw_gc_bucket_part_agg" if partition else "pw_gc_bucket_agg"
+        raise RuntimeError(f"{fn} failed: hip error {rc}")
     total, overflow = base_ctl[nb + 1 :].tolist()
     if overflow:
         return None
@@ -765,9 +900,9 @@ def _group_combine_bucket(
         ctypes.c_void_p(bounds.data_ptr()),
         ctypes.c_int(bucket_bits),
         ctypes.c_int64(total),
-        ctypes.c_void_p(staged[0].data_ptr()),
-        ctypes.c_void_p(staged[1].data_ptr()),
-        ctypes.c_void_p(scratch32[2].data_ptr()),
+        ctypes.c_void_p(staged[st0].data_ptr()),
+        ctypes.c_void_p(staged[st0 + 1].data_ptr()),
+        ctypes.c_void_p(st_first.data_ptr()),
         sarr,
         ctypes.c_int(nacc),
         ctypes.c_void_p(out_k[0].data_ptr()),
@@ -793,6 +928,7 @@ def group_combine_gpu(
     bucket_bits: int = GC_BUCKET_BITS,
     table_capacity: int | None = None,
     max_bucket_rows: int | None = None,
+    partition: bool | None = None,
 ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, list]:
     """The groupby combiner on UNSORTED interleaved keys: (n,2) int64 keys
     + up to 8 int64 contribution columns -> (uk0, uk1, first_row, accs)
@@ -812,12 +948,17 @@ def group_combine_gpu(
     result is the same on every path.
 
     `bucket=True` (off by default; the groupby node turns it on, through
-    gc_bucket_scope, when its estimate of the distinct keys fits) first tries the bucket path: one
-    radix pass on the top `bucket_bits` of word0, then one workgroup per
-    bucket aggregates its rows in an LDS table of `table_capacity` entries
-    (a power of two, default gc_bucket_capacity(nacc)) and emits its unique
-    keys in order.  It needs no order of the n rows and has one host sync
-    too.  A bucket with more than GC_BUCKET_MAX_LOAD * table_capacity
+    gc_bucket_scope, when its estimate of the distinct keys fits) first tries the bucket path: the
+    rows are grouped by the top `bucket_bits` of word0, then one workgroup
+    per bucket aggregates its rows in an LDS table of `table_capacity`
+    entries (a power of two, default gc_bucket_capacity(nacc)) and emits
+    its unique keys in order.  It needs no order of the n rows and has one
+    host sync too.  With `bucket_bits` <= 8 the grouping is a hand-written
+    partition (count, scan, scatter) that moves key, row index and
+    contributions into bucket order, so the aggregation reads them in
+    sequence; `partition=False` (or PW_NO_GC_PARTITION=1), and any larger
+    `bucket_bits`, sorts (prefix, row) pairs by bucket instead and gathers
+    the rows through the permutation.  `gc_bucket_layout_counts` says which.  A bucket with more than GC_BUCKET_MAX_LOAD * table_capacity
     distinct keys or more than `max_bucket_rows` rows (default: four times
     the even share, at least 65536) overflows, and the call goes on with
     the prefix path as if `bucket` had not been given."""
@@ -845,11 +986,15 @@ def group_combine_gpu(
             even = -(-n // (1 << bucket_bits))
             max_bucket_rows = max(GC_BUCKET_ROWS_FACTOR * even, GC_BUCKET_ROWS_FLOOR)
         assert max_bucket_rows >= 1
+        if partition is None:
+            partition = not _PW_NO_GC_PARTITION
+        partition = bool(partition) and bucket_bits <= GC_PART_MAX_BITS
         res = _group_combine_bucket(
-            lib, keys_n2, contribs, bucket_bits, cap, max_bucket_rows
+            lib, keys_n2, contribs, bucket_bits, cap, max_bucket_rows, partition
         )
         if res is not None:
             gc_path_counts["bucket"] += 1
+            gc_bucket_layout_counts["partition" if partition else "gather"] += 1
             return res
     sorted_k = torch.empty((2, n), dtype=torch.int64, device=dev)
     perm32 = torch.empty(n, dtype=torch.int32, device=dev)  # uint32 bits

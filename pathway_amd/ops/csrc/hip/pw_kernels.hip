@@ -2892,14 +2892,34 @@ extern "C" int pw_gc_prefix_sort_count(const void* keys, int64_t n, void* temp,
 // (the top bucket_bits of word0: one radix pass) and aggregates each bucket
 // in LDS:
 //
-//   partition  gc_sort_prefix with prefix_bits = bucket_bits: perm32 grouped
-//              by bucket in signed key order, rows ascending inside a bucket
-//   bounds     k_gc_bucket_bounds: the 2^bucket_bits + 1 bucket offsets by
-//              binary search in the sorted prefixes; clears the overflow word
+//   partition  bucket_bits <= 8 (the partition layout): the rows themselves
+//              are moved into bucket order, read once in row order.
+//                k_gc_part_count    per-workgroup LDS histogram of a fixed
+//                                   tile of rows, block_hist[block][bucket]
+//                k_gc_part_scan     one workgroup: bucket totals to
+//                                   bucket_start[0..nb], and the first output
+//                                   position per bucket of each of 32 ranges
+//                                   of workgroups; clears ctl[0..1]
+//                k_gc_part_scatter  the same tile again (16-B key, row index
+//                                   and every contribution): part_keys (n,2),
+//                                   part_row, part_acc[a], grouped by bucket;
+//                                   its own first positions are its range's
+//                                   plus the counts of the blocks before it
+//              The order of the rows inside a bucket is whatever the LDS
+//              cursors hand out: sums are unsigned adds and the first row is
+//              a min, so the result does not depend on it.  No sort, no
+//              memset, no temp storage.
+//              bucket_bits > 8 or the gather layout: gc_sort_prefix with
+//              prefix_bits = bucket_bits (perm32 grouped by bucket, rows
+//              ascending inside a bucket), then k_gc_bucket_bounds: the
+//              2^bucket_bits + 1 bucket offsets by binary search in the
+//              sorted prefixes; clears the overflow word
 //   aggregate  k_gc_bucket_agg: one workgroup per bucket; open-addressing
 //              table in LDS (word0, word1, nacc sums, first row), then an
 //              ordered emit of the bucket's unique keys into staging arrays
-//              at the bucket's own row offset
+//              at the bucket's own row offset.  <PART = true> reads
+//              part_keys[i], part_row[i], part_acc[a][i] in order;
+//              <PART = false> reads keys and contributions through perm32.
 //   scan       k_gc_bucket_scan: exclusive scan of the per-bucket unique
 //              counts; total and overflow word side by side for one read
 //   compact    k_gc_bucket_compact (after the host read): staged entries to
@@ -2928,6 +2948,262 @@ extern "C" int pw_gc_prefix_sort_count(const void* keys, int64_t n, void* temp,
 #define PW_GC_BK_LDS_MAX 61440      // dynamic LDS of k_gc_bucket_agg
 #define PW_GC_BK_UNROLL 4
 
+// -- the partition: count, scan, scatter --
+#define PW_GC_PT_THREADS 1024
+#define PW_GC_PT_TILE 8192         // rows per workgroup, count and scatter
+#define PW_GC_PT_ROWS (PW_GC_PT_TILE / PW_GC_PT_THREADS)
+#define PW_GC_PT_SUB 2048          // rows the staged scatter orders at a time
+#define PW_GC_PT_SCAN_RANGES 32    // block ranges of k_gc_part_scan
+
+// bucket id: the top bucket_bits of word0, sign bit flipped (as GcPrefix)
+__device__ __forceinline__ uint32_t gc_pt_bucket(unsigned long long w0,
+                                                 int drop) {
+  return ((uint32_t)(w0 >> 32) ^ 0x80000000u) >> drop;
+}
+
+// block_hist rows are padded to 8 entries, so that the scan reads 2 x uint4
+static inline uint32_t gc_pt_stride(uint32_t nb) { return nb < 8 ? 8 : nb; }
+
+// blocks per range of k_gc_part_scan
+__host__ __device__ static inline uint32_t gc_pt_chunk(uint32_t nblk) {
+  return (nblk + PW_GC_PT_SCAN_RANGES - 1) / PW_GC_PT_SCAN_RANGES;
+}
+
+__global__ __launch_bounds__(PW_GC_PT_THREADS) void k_gc_part_count(
+    const long long* __restrict__ keys, int64_t n, int drop, uint32_t nbp,
+    uint32_t* __restrict__ block_hist) {
+  __shared__ uint32_t h[256];
+  const uint32_t tid = threadIdx.x;
+  if (tid < 256) h[tid] = 0;
+  __syncthreads();
+  const int64_t base = (int64_t)blockIdx.x * PW_GC_PT_TILE + tid;
+  unsigned long long w[PW_GC_PT_ROWS];
+#pragma unroll
+  for (int q = 0; q < PW_GC_PT_ROWS; ++q) {
+    const int64_t i = base + (int64_t)q * PW_GC_PT_THREADS;
+    w[q] = i < n ? (unsigned long long)keys[2 * (size_t)i] : 0ULL;
+  }
+#pragma unroll
+  for (int q = 0; q < PW_GC_PT_ROWS; ++q) {
+    const int64_t i = base + (int64_t)q * PW_GC_PT_THREADS;
+    if (i < n) atomicAdd(&h[gc_pt_bucket(w[q], drop)], 1u);
+  }
+  __syncthreads();
+  if (tid < nbp) block_hist[(size_t)blockIdx.x * nbp + tid] = h[tid];
+}
+
+// One workgroup.  Thread (tb, tr) owns eight neighbouring buckets and one
+// of PW_GC_PT_SCAN_RANGES ranges of blocks and sums its range.  The range
+// sums are scanned per bucket and the bucket totals across buckets in LDS.
+// Output: bucket_start[0..nb], and range_base[r][b], the first output
+// position of range r in bucket b.  block_hist is read once and not
+// rewritten (rewriting it with every block's own base made this kernel move
+// three times the bytes through one CU: 21 us against 13 us of
+// k_gc_part_count at 4M rows); k_gc_part_scatter adds the counts of the at
+// most chunk - 1 blocks of its range that come before it.
+__global__ __launch_bounds__(PW_GC_PT_THREADS) void k_gc_part_scan(
+    const uint32_t* __restrict__ block_hist, uint32_t nblk, uint32_t nb,
+    uint32_t nbp, int64_t n, uint32_t* __restrict__ bucket_start,
+    uint32_t* __restrict__ range_base, unsigned long long* ctl) {
+  __shared__ uint32_t part[PW_GC_PT_SCAN_RANGES][256];
+  __shared__ uint32_t sc[256];
+  const uint32_t tid = threadIdx.x;
+  const uint32_t no = nbp / 8;  // octets of buckets
+  const uint32_t tb = tid % no, tr = tid / no;
+  const bool active = tr < PW_GC_PT_SCAN_RANGES;
+  const uint32_t chunk = gc_pt_chunk(nblk);
+  const uint32_t lo = tr * chunk < nblk ? tr * chunk : nblk;
+  const uint32_t hi = lo + chunk < nblk ? lo + chunk : nblk;
+  const uint4* h4 = (const uint4*)block_hist;
+  if (tid == 0) {
+    ctl[0] = 0;
+    ctl[1] = 0;
+  }
+  if (active) {
+    uint4 s = make_uint4(0, 0, 0, 0), t = make_uint4(0, 0, 0, 0);
+#pragma unroll 8
+    for (uint32_t blk = lo; blk < hi; ++blk) {
+      const uint4 v = h4[((size_t)blk * no + tb) * 2];
+      const uint4 w = h4[((size_t)blk * no + tb) * 2 + 1];
+      s.x += v.x, s.y += v.y, s.z += v.z, s.w += v.w;
+      t.x += w.x, t.y += w.y, t.z += w.z, t.w += w.w;
+    }
+    uint32_t* p = &part[tr][8 * tb];
+    p[0] = s.x, p[1] = s.y, p[2] = s.z, p[3] = s.w;
+    p[4] = t.x, p[5] = t.y, p[6] = t.z, p[7] = t.w;
+  }
+  __syncthreads();
+  uint32_t tot = 0;
+  if (tid < nbp) {
+    for (int r = 0; r < PW_GC_PT_SCAN_RANGES; ++r) {
+      const uint32_t v = part[r][tid];
+      part[r][tid] = tot;
+      tot += v;
+    }
+  }
+  if (tid < 256) sc[tid] = tot;
+  __syncthreads();
+  for (uint32_t off = 1; off < 256; off <<= 1) {
+    const uint32_t v = (tid < 256 && tid >= off) ? sc[tid - off] : 0;
+    __syncthreads();
+    if (tid < 256) sc[tid] += v;
+    __syncthreads();
+  }
+  if (tid < 256) {
+    const uint32_t ex = sc[tid] - tot;
+    sc[tid] = ex;  // only this thread reads or writes sc[tid] here
+    if (tid < nb) bucket_start[tid] = ex;
+  }
+  if (tid == 0) bucket_start[nb] = (uint32_t)n;
+  __syncthreads();
+  for (uint32_t e = tid; e < PW_GC_PT_SCAN_RANGES * nbp; e += PW_GC_PT_THREADS)
+    range_base[e] = sc[e % nbp] + part[e / nbp][e % nbp];
+}
+
+// STAGED = false: every row goes from registers to the position an LDS
+// cursor of its bucket hands out.  STAGED = true: PW_GC_PT_SUB rows at a
+// time are first ordered by bucket in LDS, so that a bucket's share of them
+// leaves as one contiguous run of 16-B, 8-B and 4-B stores.
+template <bool STAGED>
+__global__ __launch_bounds__(PW_GC_PT_THREADS) void k_gc_part_scatter(
+    const long long* __restrict__ keys, AccPtrs contribs, int nacc, int64_t n,
+    int drop, uint32_t nbp, const uint32_t* __restrict__ block_hist,
+    const uint32_t* __restrict__ range_base, long long* __restrict__ part_keys,
+    uint32_t* __restrict__ part_row, AccPtrsMut part_acc) {
+  __shared__ uint32_t cur[256];  // next output position per bucket
+  const uint32_t tid = threadIdx.x;
+  const ulonglong2* __restrict__ k2 = (const ulonglong2*)keys;
+  ulonglong2* __restrict__ o2 = (ulonglong2*)part_keys;
+  const long long* __restrict__ c0 = contribs.p[0];
+  const int64_t tile = (int64_t)blockIdx.x * PW_GC_PT_TILE;
+  if (tid < nbp) {
+    // this block's first position: its range's, plus the blocks before it
+    const uint32_t chunk = gc_pt_chunk(gridDim.x);
+    const uint32_t r = blockIdx.x / chunk;
+    uint32_t v = range_base[r * nbp + tid];
+    for (uint32_t blk = r * chunk; blk < blockIdx.x; ++blk)
+      v += block_hist[(size_t)blk * nbp + tid];
+    cur[tid] = v;
+  }
+  if constexpr (!STAGED) {
+    __syncthreads();
+    for (int g = 0; g < PW_GC_PT_ROWS; g += 4) {
+      ulonglong2 kv[4];
+      long long v0[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int64_t i = tile + (int64_t)(g + q) * PW_GC_PT_THREADS + tid;
+        if (i < n) {
+          kv[q] = k2[i];
+          v0[q] = nacc > 0 ? c0[i] : 0;
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int64_t i = tile + (int64_t)(g + q) * PW_GC_PT_THREADS + tid;
+        if (i >= n) continue;
+        const uint32_t dst = atomicAdd(&cur[gc_pt_bucket(kv[q].x, drop)], 1u);
+        o2[dst] = kv[q];
+        part_row[dst] = (uint32_t)i;
+        if (nacc > 0) part_acc.p[0][dst] = v0[q];
+        for (int a = 1; a < nacc; ++a) part_acc.p[a][dst] = contribs.p[a][i];
+      }
+    }
+  } else {
+    constexpr int SQ = PW_GC_PT_SUB / PW_GC_PT_THREADS;  // rows per thread
+    __shared__ ulonglong2 bufk[PW_GC_PT_SUB];
+    __shared__ long long bufa[PW_GC_PT_SUB];
+    __shared__ uint32_t bufr[PW_GC_PT_SUB];
+    __shared__ uint8_t bkt[PW_GC_PT_SUB];
+    __shared__ uint32_t cnt[256], lstart[256], delta[256], wtot[4];
+    for (int64_t sbase = tile; sbase < tile + PW_GC_PT_TILE && sbase < n;
+         sbase += PW_GC_PT_SUB) {
+      const uint32_t m =
+          n - sbase < PW_GC_PT_SUB ? (uint32_t)(n - sbase) : PW_GC_PT_SUB;
+      if (tid < 256) cnt[tid] = 0;
+      __syncthreads();
+      ulonglong2 kv[SQ];
+      long long v0[SQ];
+      uint32_t bk[SQ], lp[SQ];
+#pragma unroll
+      for (int q = 0; q < SQ; ++q) {
+        const uint32_t j = q * PW_GC_PT_THREADS + tid;
+        if (j < m) {
+          kv[q] = k2[sbase + j];
+          v0[q] = nacc > 0 ? c0[sbase + j] : 0;
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < SQ; ++q) {
+        const uint32_t j = q * PW_GC_PT_THREADS + tid;
+        if (j < m) {
+          bk[q] = gc_pt_bucket(kv[q].x, drop);
+          lp[q] = atomicAdd(&cnt[bk[q]], 1u);  // rank inside the bucket
+        }
+      }
+      __syncthreads();
+      // exclusive scan of the 256 counts: four waves, then their totals
+      uint32_t c = 0, inc = 0;
+      if (tid < 256) {
+        c = cnt[tid];
+        inc = c;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+          const uint32_t up = __shfl_up(inc, d);
+          if ((tid & 63) >= (uint32_t)d) inc += up;
+        }
+        if ((tid & 63) == 63) wtot[tid >> 6] = inc;
+      }
+      __syncthreads();
+      if (tid < 256) {
+        uint32_t off = 0;
+        for (uint32_t w = 0; w < (tid >> 6); ++w) off += wtot[w];
+        const uint32_t ex = off + inc - c;
+        lstart[tid] = ex;
+        delta[tid] = cur[tid] - ex;  // output position = delta + LDS position
+        cur[tid] += c;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int q = 0; q < SQ; ++q) {
+        const uint32_t j = q * PW_GC_PT_THREADS + tid;
+        if (j < m) {
+          lp[q] += lstart[bk[q]];
+          bufk[lp[q]] = kv[q];
+          bufr[lp[q]] = (uint32_t)(sbase + j);
+          bkt[lp[q]] = (uint8_t)bk[q];
+          if (nacc > 0) bufa[lp[q]] = v0[q];
+        }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int q = 0; q < SQ; ++q) {
+        const uint32_t j = q * PW_GC_PT_THREADS + tid;
+        if (j < m) {
+          const uint32_t dst = delta[bkt[j]] + j;
+          o2[dst] = bufk[j];
+          part_row[dst] = bufr[j];
+          if (nacc > 0) part_acc.p[0][dst] = bufa[j];
+        }
+      }
+      for (int a = 1; a < nacc; ++a) {
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < SQ; ++q) {
+          const uint32_t j = q * PW_GC_PT_THREADS + tid;
+          if (j < m) bufa[lp[q]] = contribs.p[a][sbase + j];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < SQ; ++q) {
+          const uint32_t j = q * PW_GC_PT_THREADS + tid;
+          if (j < m) part_acc.p[a][delta[bkt[j]] + j] = bufa[j];
+        }
+      }
+    }
+  }
+}
+
 __global__ void k_gc_bucket_bounds(const uint32_t* __restrict__ prefix_sorted,
                                    int64_t n, uint32_t nb,
                                    uint32_t* bucket_start,
@@ -2954,8 +3230,18 @@ __device__ __forceinline__ uint32_t gc_bk_hash(unsigned long long w0,
   return (h * 0x85EBCA6Bu) >> (32 - lg_cap);
 }
 
+// PART = false: perm32 lists the rows of every bucket; keys and contribs are
+// the caller's arrays, read through it (NV = 1: the first contribution is
+// loaded with the key, the others when the slot is found).
+// PART = true: perm32 is part_row, part_keys the partitioned keys, contribs
+// the partitioned columns, all read at position i; NV is the number of
+// columns held in registers (1 or 8, at least nacc).  keys stays the
+// caller's array: slots are claimed with the original row index, and the
+// rare read of a claimed slot's key goes there.
+template <bool PART, int NV>
 __global__ __launch_bounds__(PW_GC_BK_THREADS) void k_gc_bucket_agg(
     const long long* __restrict__ keys, const uint32_t* __restrict__ perm32,
+    const long long* __restrict__ part_keys,
     const uint32_t* __restrict__ bucket_start, AccPtrs contribs, int nacc,
     int bucket_bits, uint32_t cap, int lg_cap, uint32_t max_distinct,
     uint32_t max_rows, uint32_t max_probe, long long* st_k0, long long* st_k1,
@@ -2998,7 +3284,7 @@ __global__ __launch_bounds__(PW_GC_BK_THREADS) void k_gc_bucket_agg(
     uint32_t row[PW_GC_BK_UNROLL];
     unsigned long long k0[PW_GC_BK_UNROLL];
     long long k1[PW_GC_BK_UNROLL];
-    unsigned long long v0[PW_GC_BK_UNROLL];
+    unsigned long long v[PW_GC_BK_UNROLL][NV];
 #pragma unroll
     for (int q = 0; q < PW_GC_BK_UNROLL; ++q) {
       int64_t i = base + (int64_t)q * PW_GC_BK_THREADS;
@@ -3007,9 +3293,19 @@ __global__ __launch_bounds__(PW_GC_BK_THREADS) void k_gc_bucket_agg(
 #pragma unroll
     for (int q = 0; q < PW_GC_BK_UNROLL; ++q) {
       if (row[q] == PW_GC_BK_UNPUB) continue;
-      k0[q] = (unsigned long long)keys[2 * (size_t)row[q]];
-      k1[q] = keys[2 * (size_t)row[q] + 1];
-      v0[q] = nacc > 0 ? (unsigned long long)c0[row[q]] : 0ULL;
+      if constexpr (PART) {
+        const int64_t i = base + (int64_t)q * PW_GC_BK_THREADS;
+        const ulonglong2 kv = ((const ulonglong2*)part_keys)[i];
+        k0[q] = kv.x;
+        k1[q] = (long long)kv.y;
+#pragma unroll
+        for (int a = 0; a < NV; ++a)
+          v[q][a] = a < nacc ? (unsigned long long)contribs.p[a][i] : 0ULL;
+      } else {
+        k0[q] = (unsigned long long)keys[2 * (size_t)row[q]];
+        k1[q] = keys[2 * (size_t)row[q] + 1];
+        v[q][0] = nacc > 0 ? (unsigned long long)c0[row[q]] : 0ULL;
+      }
     }
 #pragma unroll
     for (int q = 0; q < PW_GC_BK_UNROLL; ++q) {
@@ -3046,10 +3342,16 @@ __global__ __launch_bounds__(PW_GC_BK_THREADS) void k_gc_bucket_agg(
           }
         }
         if (match) {
-          if (nacc > 0) atomicAdd(&tacc[slot], v0[q]);
-          for (int a = 1; a < nacc; ++a)
-            atomicAdd(&tacc[(size_t)a * cap + slot],
-                      (unsigned long long)contribs.p[a][row[q]]);
+          if (nacc > 0) atomicAdd(&tacc[slot], v[q][0]);
+          if constexpr (PART) {
+#pragma unroll
+            for (int a = 1; a < NV; ++a)
+              if (a < nacc) atomicAdd(&tacc[(size_t)a * cap + slot], v[q][a]);
+          } else {
+            for (int a = 1; a < nacc; ++a)
+              atomicAdd(&tacc[(size_t)a * cap + slot],
+                        (unsigned long long)contribs.p[a][row[q]]);
+          }
           done = true;
           break;
         }
@@ -3209,9 +3511,140 @@ extern "C" int pw_gc_bucket_agg(const void* keys, int64_t n, void* temp,
                      dim3((nb + 1 + PW_BLOCK - 1) / PW_BLOCK), dim3(PW_BLOCK),
                      0, s, (const uint32_t*)prefix_scratch, n, nb,
                      (uint32_t*)bucket_start, (unsigned long long*)ctl);
-  hipLaunchKernelGGL(k_gc_bucket_agg, dim3(nb), dim3(PW_GC_BK_THREADS), lds, s,
-                     (const long long*)keys, (const uint32_t*)perm32,
+  hipLaunchKernelGGL((k_gc_bucket_agg<false, 1>), dim3(nb),
+                     dim3(PW_GC_BK_THREADS), lds, s, (const long long*)keys,
+                     (const uint32_t*)perm32, (const long long*)nullptr,
                      (const uint32_t*)bucket_start, cp, nacc, bucket_bits,
+                     (uint32_t)table_capacity, lg_cap, (uint32_t)max_distinct,
+                     (uint32_t)max_bucket_rows, (uint32_t)max_probe,
+                     (long long*)st_k0, (long long*)st_k1, (uint32_t*)st_first,
+                     sp, (uint32_t*)bucket_uniques, (unsigned long long*)ctl);
+  hipLaunchKernelGGL(k_gc_bucket_scan, dim3(1), dim3(PW_BLOCK), 0, s,
+                     (const uint32_t*)bucket_uniques, nb, (long long*)base,
+                     (unsigned long long*)ctl);
+  return (int)hipGetLastError();
+}
+
+// rows per workgroup of the partition kernels
+extern "C" int64_t pw_gc_part_tile() { return PW_GC_PT_TILE; }
+
+// uint32 entries of block_hist, with the scan's range_base behind it, for n
+// rows (0: not a partition case)
+extern "C" int64_t pw_gc_part_hist_entries(int64_t n, int bucket_bits) {
+  if (n < 2 || n >= ((int64_t)1 << 32) - 1) return 0;
+  if (bucket_bits < 1 || bucket_bits > 8) return 0;
+  int64_t nblk = (n + PW_GC_PT_TILE - 1) / PW_GC_PT_TILE;
+  return (nblk + PW_GC_PT_SCAN_RANGES) *
+         (int64_t)gc_pt_stride(1u << bucket_bits);
+}
+
+// count + scan + scatter on stream s; arguments checked by the callers
+static void gc_partition_launch(const long long* keys, int64_t n,
+                                int bucket_bits, const AccPtrs& cp, int nacc,
+                                uint32_t* block_hist, long long* part_keys,
+                                uint32_t* part_row, const AccPtrsMut& pp,
+                                uint32_t* bucket_start,
+                                unsigned long long* ctl, int direct,
+                                hipStream_t s) {
+  const uint32_t nb = 1u << bucket_bits, nbp = gc_pt_stride(nb);
+  const uint32_t nblk = (uint32_t)((n + PW_GC_PT_TILE - 1) / PW_GC_PT_TILE);
+  const int drop = 32 - bucket_bits;
+  uint32_t* range_base = block_hist + (size_t)nblk * nbp;
+  hipLaunchKernelGGL(k_gc_part_count, dim3(nblk), dim3(PW_GC_PT_THREADS), 0, s,
+                     keys, n, drop, nbp, block_hist);
+  hipLaunchKernelGGL(k_gc_part_scan, dim3(1), dim3(PW_GC_PT_THREADS), 0, s,
+                     (const uint32_t*)block_hist, nblk, nb, nbp, n,
+                     bucket_start, range_base, ctl);
+  if (direct)
+    hipLaunchKernelGGL(k_gc_part_scatter<false>, dim3(nblk),
+                       dim3(PW_GC_PT_THREADS), 0, s, keys, cp, nacc, n, drop,
+                       nbp, (const uint32_t*)block_hist,
+                       (const uint32_t*)range_base, part_keys, part_row, pp);
+  else
+    hipLaunchKernelGGL(k_gc_part_scatter<true>, dim3(nblk),
+                       dim3(PW_GC_PT_THREADS), 0, s, keys, cp, nacc, n, drop,
+                       nbp, (const uint32_t*)block_hist,
+                       (const uint32_t*)range_base, part_keys, part_row, pp);
+}
+
+static bool gc_partition_args_ok(const void* keys, int64_t n, int bucket_bits,
+                                 int nacc, const void* block_hist,
+                                 const void* part_keys) {
+  if (n < 2 || n >= ((int64_t)1 << 32) - 1) return false;
+  if (bucket_bits < 1 || bucket_bits > 8) return false;
+  if (nacc < 0 || nacc > 8) return false;
+  // 128-bit loads and stores
+  return ((uintptr_t)keys | (uintptr_t)block_hist | (uintptr_t)part_keys) % 16 == 0;
+}
+
+// The partition alone (tests).  keys: (n,2) int64, 16-B aligned; block_hist:
+// pw_gc_part_hist_entries uint32, 16-B aligned; part_keys: (n,2) int64;
+// part_row: n uint32; part_acc[a]: n int64; bucket_start: nb+1 uint32; ctl:
+// 2 uint64, cleared.  direct != 0 scatters from registers (A/B runs).
+extern "C" int pw_gc_partition(const void* keys, int64_t n, int bucket_bits,
+                               const void** contrib_ptrs, int nacc,
+                               void* block_hist, void* part_keys,
+                               void* part_row, void** part_acc_ptrs,
+                               void* bucket_start, void* ctl, int direct,
+                               void* stream) {
+  if (!gc_partition_args_ok(keys, n, bucket_bits, nacc, block_hist, part_keys))
+    return 1;
+  AccPtrs cp;
+  AccPtrsMut pp;
+  for (int a = 0; a < 8; ++a) {
+    cp.p[a] = a < nacc ? (const long long*)contrib_ptrs[a] : nullptr;
+    pp.p[a] = a < nacc ? (long long*)part_acc_ptrs[a] : nullptr;
+  }
+  gc_partition_launch((const long long*)keys, n, bucket_bits, cp, nacc,
+                      (uint32_t*)block_hist, (long long*)part_keys,
+                      (uint32_t*)part_row, pp, (uint32_t*)bucket_start,
+                      (unsigned long long*)ctl, direct, (hipStream_t)stream);
+  return (int)hipGetLastError();
+}
+
+// pw_gc_bucket_agg on the partition layout (bucket_bits <= 8): partition +
+// aggregate + scan on the caller's stream; no temp, prefix scratch or
+// perm32.  Partition arguments as pw_gc_partition, the others as
+// pw_gc_bucket_agg; pw_gc_bucket_compact follows the same host read.
+extern "C" int pw_gc_bucket_part_agg(
+    const void* keys, int64_t n, int bucket_bits, int64_t table_capacity,
+    int64_t max_distinct, int64_t max_bucket_rows, int64_t max_probe,
+    const void** contrib_ptrs, int nacc, void* block_hist, void* part_keys,
+    void* part_row, void** part_acc_ptrs, void* bucket_start,
+    void* bucket_uniques, void* base, void* st_k0, void* st_k1, void* st_first,
+    void** st_acc_ptrs, void* ctl, int direct, void* stream) {
+  if (!gc_partition_args_ok(keys, n, bucket_bits, nacc, block_hist, part_keys))
+    return 1;
+  if (table_capacity < 2 || table_capacity > 32768 ||
+      (table_capacity & (table_capacity - 1)))
+    return 1;
+  size_t lds = (size_t)table_capacity * gc_bk_entry_bytes(nacc);
+  if (lds > PW_GC_BK_LDS_MAX) return 1;
+  if (max_distinct < 1 || max_distinct > table_capacity) return 1;
+  if (max_bucket_rows < 1 || max_probe < 1) return 1;
+  if (max_bucket_rows > 0xFFFFFFFFLL) max_bucket_rows = 0xFFFFFFFFLL;
+  if (max_probe > table_capacity) max_probe = table_capacity;
+  int lg_cap = 0;
+  while (((int64_t)1 << lg_cap) < table_capacity) ++lg_cap;
+  hipStream_t s = (hipStream_t)stream;
+  AccPtrs cp, pc;
+  AccPtrsMut pp, sp;
+  for (int a = 0; a < 8; ++a) {
+    cp.p[a] = a < nacc ? (const long long*)contrib_ptrs[a] : nullptr;
+    pp.p[a] = a < nacc ? (long long*)part_acc_ptrs[a] : nullptr;
+    pc.p[a] = pp.p[a];
+    sp.p[a] = a < nacc ? (long long*)st_acc_ptrs[a] : nullptr;
+  }
+  gc_partition_launch((const long long*)keys, n, bucket_bits, cp, nacc,
+                      (uint32_t*)block_hist, (long long*)part_keys,
+                      (uint32_t*)part_row, pp, (uint32_t*)bucket_start,
+                      (unsigned long long*)ctl, direct, s);
+  const uint32_t nb = 1u << bucket_bits;
+  auto agg = nacc <= 1 ? k_gc_bucket_agg<true, 1> : k_gc_bucket_agg<true, 8>;
+  hipLaunchKernelGGL(agg, dim3(nb), dim3(PW_GC_BK_THREADS), lds, s,
+                     (const long long*)keys, (const uint32_t*)part_row,
+                     (const long long*)part_keys,
+                     (const uint32_t*)bucket_start, pc, nacc, bucket_bits,
                      (uint32_t)table_capacity, lg_cap, (uint32_t)max_distinct,
                      (uint32_t)max_bucket_rows, (uint32_t)max_probe,
                      (long long*)st_k0, (long long*)st_k1, (uint32_t*)st_first,

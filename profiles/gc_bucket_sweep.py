@@ -1,5 +1,6 @@
-"""Op-level timings of ops.group_combine_gpu for profiles/wordcount_r07.md:
-a sweep of bucket_bits x table_capacity at the timed size of bench.py (4M
+"""Op-level timings of ops.group_combine_gpu for profiles/wordcount_r07.md
+and wordcount_r10.md: a sweep of bucket_bits x table_capacity x layout
+(partition, or sort and gather) at the timed size of bench.py (4M
 rows, 50k distinct keys, one sum), and the bad case, an all-distinct 4M-row
 batch with the bucket path forced on (wasted pass, then the prefix path)
 and off.  Medians of 20 calls after 3 warm-up calls, host sync included.
@@ -41,9 +42,14 @@ def main():
     print(json.dumps({"case": "50k distinct", "bucket": False, "ms": ms, "path": path}))
     for bits in (6, 8, 9, 10, 12):
         for cap in (512, 1024, 2048):
-            ms, path = timed(keys, ones, bucket=True, bucket_bits=bits, table_capacity=cap)
-            print(json.dumps({"case": "50k distinct", "bucket_bits": bits,
-                              "table_capacity": cap, "ms": ms, "path": path}))
+            # both layouts where the partition serves the bucket count
+            for part in ((True, False) if bits <= ops.GC_PART_MAX_BITS else (False,)):
+                ms, path = timed(keys, ones, bucket=True, bucket_bits=bits,
+                                 table_capacity=cap, partition=part)
+                print(json.dumps({"case": "50k distinct", "bucket_bits": bits,
+                                  "table_capacity": cap,
+                                  "layout": "partition" if part else "gather",
+                                  "ms": ms, "path": path}))
     distinct = torch.randint(-(1 << 63), (1 << 63) - 1, (N, 2), generator=g).cuda()
     for on in (False, True):
         ms, path = timed(distinct, ones, bucket=on)
