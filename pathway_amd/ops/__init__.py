@@ -108,8 +108,10 @@ def varlen_hash_gpu(
     n = offsets.shape[0] - 1
     lo = torch.empty(n, dtype=torch.int64, device=bytes_t.device)
     hi = torch.empty(n, dtype=torch.int64, device=bytes_t.device)
+    bytes_t = bytes_t.contiguous()
     rc = lib.pw_varlen_hash(
-        ctypes.c_void_p(bytes_t.contiguous().data_ptr()),
+        ctypes.c_void_p(bytes_t.data_ptr()),
+        ctypes.c_int64(bytes_t.numel()),
         ctypes.c_void_p(offsets.contiguous().data_ptr()),
         ctypes.c_uint64(tag),
         ctypes.c_int64(n),
@@ -418,8 +420,10 @@ def varlen_hash_se_gpu(
     n = starts.shape[0]
     lo = torch.empty(n, dtype=torch.int64, device=bytes_t.device)
     hi = torch.empty(n, dtype=torch.int64, device=bytes_t.device)
+    bytes_t = bytes_t.contiguous()
     rc = lib.pw_varlen_hash_se(
-        ctypes.c_void_p(bytes_t.contiguous().data_ptr()),
+        ctypes.c_void_p(bytes_t.data_ptr()),
+        ctypes.c_int64(bytes_t.numel()),
         ctypes.c_void_p(starts.contiguous().data_ptr()),
         ctypes.c_void_p(ends.contiguous().data_ptr()),
         ctypes.c_uint64(tag),
@@ -1881,12 +1885,21 @@ def gather_spans_gpu(
         raise RuntimeError(f"pw_gather_spans failed: hip error {rc}")
 
 
+#: int64 words per hash-table slot, (lo, hi, val, unused) — HT_SLOT_WORDS of
+#: pw_kernels.hip
+HT_SLOT_WORDS = 4
+
+
 class DeviceHashTable:
     """Open-addressing device hash table over 128-bit keys -> int64 values
     (k_ht_build / k_ht_probe / k_ht_intern_*).  Build from a dictionary's
     hash arrays; probe per delta batch (closed world) or intern per delta
     batch (unseen keys are inserted).  Load factor <= 0.5 (nslots = next
-    pow2 >= 2m)."""
+    pow2 >= 2m).
+
+    The table is one (nslots, HT_SLOT_WORDS) int64 tensor, `tab`; tab_lo,
+    tab_hi and tab_val are its column views (shape (nslots,), strided), so
+    in-place updates through them reach the table."""
 
     def __init__(self, klo: torch.Tensor, khi: torch.Tensor,
                  vals: torch.Tensor | None = None, reserve: int = 0):
@@ -1906,10 +1919,13 @@ class DeviceHashTable:
         return 1 << max(4, (2 * m - 1).bit_length()) if m else 16
 
     def _alloc(self, device) -> None:
-        nslots = self.nslots
-        self.tab_lo = torch.empty(nslots, dtype=torch.int64, device=device)
-        self.tab_hi = torch.empty(nslots, dtype=torch.int64, device=device)
-        self.tab_val = torch.full((nslots,), -1, dtype=torch.int64, device=device)
+        if require_lib().pw_ht_slot_words() != HT_SLOT_WORDS:
+            raise RuntimeError("libpwhip.so was built for another HT_SLOT_WORDS")
+        self.tab = torch.full((self.nslots, HT_SLOT_WORDS), -1,
+                              dtype=torch.int64, device=device)
+        self.tab_lo = self.tab[:, 0]
+        self.tab_hi = self.tab[:, 1]
+        self.tab_val = self.tab[:, 2]
 
     def insert(self, klo: torch.Tensor, khi: torch.Tensor,
                vals: torch.Tensor | None = None) -> None:
@@ -1926,9 +1942,7 @@ class DeviceHashTable:
             ctypes.c_void_p(khi.data_ptr()),
             ctypes.c_void_p(vals.data_ptr()) if vals is not None else None,
             ctypes.c_int64(m),
-            ctypes.c_void_p(self.tab_lo.data_ptr()),
-            ctypes.c_void_p(self.tab_hi.data_ptr()),
-            ctypes.c_void_p(self.tab_val.data_ptr()),
+            ctypes.c_void_p(self.tab.data_ptr()),
             ctypes.c_int64(self.nslots),
             _stream_ptr(),
         )
@@ -1994,13 +2008,9 @@ class DeviceHashTable:
             ctypes.c_void_p(qlo.data_ptr()),
             ctypes.c_void_p(qhi.data_ptr()),
             ctypes.c_int64(n),
-            ctypes.c_void_p(self.tab_lo.data_ptr()),
-            ctypes.c_void_p(self.tab_hi.data_ptr()),
-            ctypes.c_void_p(self.tab_val.data_ptr()),
+            ctypes.c_void_p(self.tab.data_ptr()),
             ctypes.c_int64(self.nslots),
-            ctypes.c_void_p(front.tab_lo.data_ptr() if front else None),
-            ctypes.c_void_p(front.tab_hi.data_ptr() if front else None),
-            ctypes.c_void_p(front.tab_val.data_ptr() if front else None),
+            ctypes.c_void_p(front.tab.data_ptr() if front else None),
             ctypes.c_int64(front.nslots if front else 0),
             ctypes.c_void_p(base.data_ptr()),
             ctypes.c_void_p(pool_lo.data_ptr()),
@@ -2037,9 +2047,7 @@ class DeviceHashTable:
             ctypes.c_void_p(qlo.contiguous().data_ptr()),
             ctypes.c_void_p(qhi.contiguous().data_ptr()),
             ctypes.c_int64(nq),
-            ctypes.c_void_p(self.tab_lo.data_ptr()),
-            ctypes.c_void_p(self.tab_hi.data_ptr()),
-            ctypes.c_void_p(self.tab_val.data_ptr()),
+            ctypes.c_void_p(self.tab.data_ptr()),
             ctypes.c_int64(self.nslots),
             ctypes.c_void_p(out.data_ptr()),
             ctypes.c_void_p(found.data_ptr()),

@@ -92,103 +92,29 @@ extern "C" int pw_value_hash(const void* payload, uint64_t tag, int64_t n,
   return (int)hipGetLastError();
 }
 
-__device__ uint64_t pw_xxh64_long(const uint8_t* data, int64_t n, uint64_t tag,
-                                  uint64_t seed);
-
-// varlen: hash of [tag-word || bytes[start:end]] per row.
-// One WAVE per row (rows are short strings; lanes cooperate on ≥8B chunks
-// would need a parallel xxh64 — instead lane 0 of each 8-lane group handles
-// one row: still coalesced enough for short tokens, revisit if hot).
-__global__ void k_varlen_hash(const uint8_t* bytes, const int64_t* offsets,
-                              uint64_t tag, int64_t n, uint64_t* lo,
-                              uint64_t* hi) {
+// varlen: hash of [tag-word || bytes[start:end]] per row, one row per
+// thread per round.  pw_xxh64_tagged2 walks the row once for both seeds
+// from aligned dword loads, entirely in registers (no staging buffer: a
+// run-time indexed private array is spilled to LDS or scratch).  nbytes is
+// the length of `bytes`; no load leaves [bytes, bytes + nbytes).
+__global__ __launch_bounds__(PW_BLOCK) void k_varlen_hash(
+    const uint8_t* __restrict__ bytes, int64_t nbytes,
+    const int64_t* __restrict__ offsets, uint64_t tag, int64_t n,
+    uint64_t* __restrict__ lo, uint64_t* __restrict__ hi) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
-    int64_t a = offsets[i], b = offsets[i + 1];
-    // serialize: tag as 8-byte LE word, then raw bytes
-    // compute xxh64 incrementally over the concatenation without copying:
-    // tag word is 8 bytes => for total length < 32 we replicate the python
-    // byte-path; for simplicity build a small local buffer when len<=56,
-    // else fall back to a two-part streaming evaluation.
-    uint8_t buf[64];
-    int64_t len = b - a;
-    if (len <= 56) {
-      uint64_t t = tag;
-      __builtin_memcpy(buf, &t, 8);
-      for (int64_t k = 0; k < len; ++k) buf[8 + k] = bytes[a + k];
-      lo[i] = pw_xxh64_bytes(buf, 8 + len, PW_SEED_LO);
-      hi[i] = pw_xxh64_bytes(buf, 8 + len, PW_SEED_HI);
-    } else {
-      // long string: hash in the streaming formulation
-      lo[i] = pw_xxh64_long(bytes + a, len, tag, PW_SEED_LO);
-      hi[i] = pw_xxh64_long(bytes + a, len, tag, PW_SEED_HI);
-    }
+    const int64_t a = offsets[i], b = offsets[i + 1];
+    const PwHash128 h = pw_xxh64_tagged2(bytes, nbytes, a, b - a, tag);
+    lo[i] = h.lo;
+    hi[i] = h.hi;
   }
 }
 
-// streaming xxh64 of (8-byte tag word || data[0:n]) for n+8 >= 32
-__device__ uint64_t pw_xxh64_long(const uint8_t* data, int64_t n, uint64_t tag,
-                                  uint64_t seed) {
-  // total message = 8 + n bytes, guaranteed >= 64 here
-  uint64_t v1 = seed + PW_P1 + PW_P2;
-  uint64_t v2 = seed + PW_P2;
-  uint64_t v3 = seed;
-  uint64_t v4 = seed - PW_P1;
-  // first stripe: tag + first 24 data bytes
-  uint64_t a = tag, b, c, d;
-  __builtin_memcpy(&b, data, 8);
-  __builtin_memcpy(&c, data + 8, 8);
-  __builtin_memcpy(&d, data + 16, 8);
-  v1 = pw_round(v1, a);
-  v2 = pw_round(v2, b);
-  v3 = pw_round(v3, c);
-  v4 = pw_round(v4, d);
-  int64_t i = 24;
-  while (i + 32 <= n) {
-    __builtin_memcpy(&a, data + i, 8);
-    __builtin_memcpy(&b, data + i + 8, 8);
-    __builtin_memcpy(&c, data + i + 16, 8);
-    __builtin_memcpy(&d, data + i + 24, 8);
-    v1 = pw_round(v1, a);
-    v2 = pw_round(v2, b);
-    v3 = pw_round(v3, c);
-    v4 = pw_round(v4, d);
-    i += 32;
-  }
-  uint64_t h = pw_rotl64(v1, 1) + pw_rotl64(v2, 7) + pw_rotl64(v3, 12) +
-               pw_rotl64(v4, 18);
-  h = pw_merge_round(h, v1);
-  h = pw_merge_round(h, v2);
-  h = pw_merge_round(h, v3);
-  h = pw_merge_round(h, v4);
-  h += (uint64_t)(n + 8);
-  while (i + 8 <= n) {
-    uint64_t k;
-    __builtin_memcpy(&k, data + i, 8);
-    h ^= pw_round(0, k);
-    h = pw_rotl64(h, 27) * PW_P1 + PW_P4;
-    i += 8;
-  }
-  while (i + 4 <= n) {
-    uint32_t k;
-    __builtin_memcpy(&k, data + i, 4);
-    h ^= (uint64_t)k * PW_P1;
-    h = pw_rotl64(h, 23) * PW_P2 + PW_P3;
-    i += 4;
-  }
-  while (i < n) {
-    h ^= (uint64_t)data[i] * PW_P5;
-    h = pw_rotl64(h, 11) * PW_P1;
-    i += 1;
-  }
-  return pw_avalanche(h);
-}
-
-extern "C" int pw_varlen_hash(const void* bytes, const void* offsets,
-                              uint64_t tag, int64_t n, void* lo, void* hi,
-                              void* stream) {
+extern "C" int pw_varlen_hash(const void* bytes, int64_t nbytes,
+                              const void* offsets, uint64_t tag, int64_t n,
+                              void* lo, void* hi, void* stream) {
   hipLaunchKernelGGL(k_varlen_hash, dim3(pw_grid(n)), dim3(PW_BLOCK), 0,
-                     (hipStream_t)stream, (const uint8_t*)bytes,
+                     (hipStream_t)stream, (const uint8_t*)bytes, nbytes,
                      (const int64_t*)offsets, tag, n, (uint64_t*)lo,
                      (uint64_t*)hi);
   return (int)hipGetLastError();
@@ -231,24 +157,18 @@ extern "C" void pw_host_hash128_bytes(const void* data, int64_t n,
   *hi = pw_xxh64_bytes((const uint8_t*)data, n, PW_SEED_HI);
 }
 
-// batch host hashing of varlen byte rows (string pool fills)
+// batch host hashing of varlen byte rows (string pool fills); the arena
+// holds at least offsets[n] bytes
 extern "C" void pw_host_varlen_hash(const void* bytes, const int64_t* offsets,
                                     uint64_t tag, int64_t n, uint64_t* lo,
                                     uint64_t* hi) {
   const uint8_t* b = (const uint8_t*)bytes;
+  const int64_t nbytes = n > 0 ? offsets[n] : 0;
   for (int64_t i = 0; i < n; ++i) {
-    int64_t a = offsets[i], e = offsets[i + 1];
-    int64_t len = e - a;
-    // tag word + bytes
-    uint8_t stackbuf[4096];
-    uint8_t* buf = stackbuf;
-    if (len + 8 > (int64_t)sizeof(stackbuf)) buf = new uint8_t[len + 8];
-    uint64_t t = tag;
-    __builtin_memcpy(buf, &t, 8);
-    __builtin_memcpy(buf + 8, b + a, len);
-    lo[i] = pw_xxh64_bytes(buf, len + 8, PW_SEED_LO);
-    hi[i] = pw_xxh64_bytes(buf, len + 8, PW_SEED_HI);
-    if (buf != stackbuf) delete[] buf;
+    const int64_t a = offsets[i], e = offsets[i + 1];
+    const PwHash128 h = pw_xxh64_tagged2(b, nbytes, a, e - a, tag);
+    lo[i] = h.lo;
+    hi[i] = h.hi;
   }
 }
 
@@ -424,33 +344,27 @@ extern "C" int pw_pool_hash(const void* codes, const void* pool_lo,
 }
 
 // varlen hash with explicit [start, end) per row (token parse output —
-// tokens exclude separators so rows are not contiguous)
-__global__ void k_varlen_hash_se(const uint8_t* bytes, const int64_t* starts,
-                                 const int64_t* ends, uint64_t tag, int64_t n,
-                                 uint64_t* lo, uint64_t* hi) {
+// tokens exclude separators so rows are not contiguous); see k_varlen_hash
+__global__ __launch_bounds__(PW_BLOCK) void k_varlen_hash_se(
+    const uint8_t* __restrict__ bytes, int64_t nbytes,
+    const int64_t* __restrict__ starts, const int64_t* __restrict__ ends,
+    uint64_t tag, int64_t n, uint64_t* __restrict__ lo,
+    uint64_t* __restrict__ hi) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
-    int64_t a = starts[i], b = ends[i];
-    uint8_t buf[64];
-    int64_t len = b - a;
-    if (len <= 56) {
-      uint64_t t = tag;
-      __builtin_memcpy(buf, &t, 8);
-      for (int64_t k = 0; k < len; ++k) buf[8 + k] = bytes[a + k];
-      lo[i] = pw_xxh64_bytes(buf, 8 + len, PW_SEED_LO);
-      hi[i] = pw_xxh64_bytes(buf, 8 + len, PW_SEED_HI);
-    } else {
-      lo[i] = pw_xxh64_long(bytes + a, len, tag, PW_SEED_LO);
-      hi[i] = pw_xxh64_long(bytes + a, len, tag, PW_SEED_HI);
-    }
+    const int64_t a = starts[i], b = ends[i];
+    const PwHash128 h = pw_xxh64_tagged2(bytes, nbytes, a, b - a, tag);
+    lo[i] = h.lo;
+    hi[i] = h.hi;
   }
 }
 
-extern "C" int pw_varlen_hash_se(const void* bytes, const void* starts,
-                                 const void* ends, uint64_t tag, int64_t n,
-                                 void* lo, void* hi, void* stream) {
+extern "C" int pw_varlen_hash_se(const void* bytes, int64_t nbytes,
+                                 const void* starts, const void* ends,
+                                 uint64_t tag, int64_t n, void* lo, void* hi,
+                                 void* stream) {
   hipLaunchKernelGGL(k_varlen_hash_se, dim3(pw_grid(n)), dim3(PW_BLOCK), 0,
-                     (hipStream_t)stream, (const uint8_t*)bytes,
+                     (hipStream_t)stream, (const uint8_t*)bytes, nbytes,
                      (const int64_t*)starts, (const int64_t*)ends, tag, n,
                      (uint64_t*)lo, (uint64_t*)hi);
   return (int)hipGetLastError();
@@ -2009,110 +1923,205 @@ __global__ void k_gather_cols(const long long* __restrict__ idx, int64_t m,
 // Values are int64 >= 0; slot value -1 means empty.  Build never reads
 // keys (inputs are unique), so a single atomicCAS on the value slot
 // claims it.
+//
+// Layout: one int64 array of nslots slots of HT_SLOT_WORDS words each,
+// (lo, hi, val, unused).  With 4 words a slot is 32 bytes and never
+// straddles a cache line, so a probed slot costs one line where three
+// parallel arrays cost three; the key pair is one 16-byte load and the
+// value one 8-byte load, issued together.  All kernels address the table
+// through PwHt; the Python side (ops.HT_SLOT_WORDS) mirrors the one
+// constant.  val stays 8-byte aligned for the atomics.
+
+#define HT_SLOT_WORDS 4
+// independent queries per thread of k_ht_probe (1, 2 and 4 were measured,
+// profiles/wordcount_r11.md)
+#define PW_HT_PROBE_Q 2
+#define HT_WORD_VAL 2
+
+extern "C" int pw_ht_slot_words() { return HT_SLOT_WORDS; }
+
+struct PwHtKey {
+  long long lo, hi;
+};
+
+static_assert(HT_SLOT_WORDS % 2 == 0, "16-byte key loads need even slots");
+
+struct PwHt {
+  long long* w;
+  __device__ __forceinline__ long long* slot(uint64_t s) const {
+    return w + s * HT_SLOT_WORDS;
+  }
+  __device__ __forceinline__ long long* val(uint64_t s) const {
+    return slot(s) + HT_WORD_VAL;
+  }
+  __device__ __forceinline__ PwHtKey key(uint64_t s) const {
+    // slots are 16-byte aligned: one 16-byte load
+    const longlong2 v = *(const longlong2*)slot(s);
+    PwHtKey k;
+    k.lo = v.x, k.hi = v.y;
+    return k;
+  }
+  __device__ __forceinline__ void set_key(uint64_t s, long long lo,
+                                          long long hi) const {
+    longlong2 v;
+    v.x = lo, v.y = hi;
+    *(longlong2*)slot(s) = v;
+  }
+};
 
 __global__ void k_ht_build(const int64_t* __restrict__ klo,
                            const int64_t* __restrict__ khi,
                            const int64_t* __restrict__ vals, int64_t m,
-                           int64_t* tab_lo, int64_t* tab_hi,
-                           long long* tab_val, int64_t mask) {
+                           PwHt tab, int64_t mask) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (; i < m; i += stride) {
     uint64_t slot = (uint64_t)klo[i] & (uint64_t)mask;
-    while (atomicCAS((unsigned long long*)&tab_val[slot],
+    while (atomicCAS((unsigned long long*)tab.val(slot),
                      (unsigned long long)(long long)-1,
                      (unsigned long long)(long long)(vals ? vals[i] : i)) !=
            (unsigned long long)(long long)-1)
       slot = (slot + 1) & (uint64_t)mask;
-    tab_lo[slot] = klo[i];
-    tab_hi[slot] = khi[i];
+    tab.set_key(slot, klo[i], khi[i]);
   }
 }
 
-__global__ void k_ht_probe(const int64_t* __restrict__ qlo,
-                           const int64_t* __restrict__ qhi, int64_t nq,
-                           const int64_t* __restrict__ tab_lo,
-                           const int64_t* __restrict__ tab_hi,
-                           const long long* __restrict__ tab_val,
-                           int64_t mask, int64_t* out, bool* found) {
+// Read-only probe of one key (the front table of k_ht_intern_claim): the
+// stored value, or -1.  A slot's key and value are loaded together and
+// tested afterwards (one trip to L2 per probed slot).  At most max_probes
+// slots are examined.
+__device__ __forceinline__ long long pw_ht_find(const PwHt tab, uint64_t mask,
+                                                long long lo, long long hi,
+                                                int64_t max_probes) {
+  uint64_t slot = (uint64_t)lo & mask;
+  for (int64_t probes = 0; probes < max_probes; ++probes) {
+    const PwHtKey k = tab.key(slot);
+    const long long tv = *tab.val(slot);
+    if (tv < 0) return -1;  // empty -> miss
+    if (k.lo == lo && k.hi == hi) return tv;
+    slot = (slot + 1) & mask;
+  }
+  return -1;
+}
+
+__global__ __launch_bounds__(PW_BLOCK) void k_ht_probe(
+    const int64_t* __restrict__ qlo, const int64_t* __restrict__ qhi,
+    int64_t nq, const PwHt tab, int64_t mask, int64_t* __restrict__ out,
+    bool* __restrict__ found) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (; i < nq; i += stride) {
-    int64_t lo = qlo[i], hi = qhi[i];
-    uint64_t slot = (uint64_t)lo & (uint64_t)mask;
-    int64_t v = -1;
-    for (;;) {
-      long long tv = tab_val[slot];
-      if (tv == -1) break;  // empty -> miss
-      if (tab_lo[slot] == lo && tab_hi[slot] == hi) {
-        v = (int64_t)tv;
-        break;
-      }
-      slot = (slot + 1) & (uint64_t)mask;
+  // PW_HT_PROBE_Q independent queries per thread; every round issues the
+  // slot loads (key pair and value) of all of them, then tests.  As in the
+  // front-table walk of k_ht_intern_claim, any negative value ends a walk
+  // as a miss (-1 empty, <= -2 a pending slot left by a flagged intern
+  // error), and a walk stops after nslots probes (a full table).
+  for (; i < nq; i += stride * PW_HT_PROBE_Q) {
+    long long lo[PW_HT_PROBE_Q], hi[PW_HT_PROBE_Q], v[PW_HT_PROBE_Q];
+    uint64_t slot[PW_HT_PROBE_Q];
+    bool live[PW_HT_PROBE_Q];
+    bool any = false;
+#pragma unroll
+    for (int q = 0; q < PW_HT_PROBE_Q; ++q) {
+      const int64_t j = i + q * stride;
+      live[q] = j < nq;
+      lo[q] = live[q] ? qlo[j] : 0;
+      hi[q] = live[q] ? qhi[j] : 0;
+      slot[q] = (uint64_t)lo[q] & (uint64_t)mask;
+      v[q] = -1;
+      any |= live[q];
     }
-    out[i] = v;
-    found[i] = v != -1;
+    for (int64_t probes = 0; any && probes <= mask; ++probes) {
+      PwHtKey k[PW_HT_PROBE_Q];
+      long long tv[PW_HT_PROBE_Q];
+#pragma unroll
+      for (int q = 0; q < PW_HT_PROBE_Q; ++q)
+        if (live[q]) {
+          k[q] = tab.key(slot[q]);
+          tv[q] = *tab.val(slot[q]);
+        }
+      any = false;
+#pragma unroll
+      for (int q = 0; q < PW_HT_PROBE_Q; ++q)
+        if (live[q]) {
+          if (tv[q] < 0) {
+            live[q] = false;
+          } else if (k[q].lo == lo[q] && k[q].hi == hi[q]) {
+            v[q] = tv[q];
+            live[q] = false;
+          } else {
+            slot[q] = (slot[q] + 1) & (uint64_t)mask;
+            any = true;
+          }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < PW_HT_PROBE_Q; ++q) {
+      const int64_t j = i + q * stride;
+      if (j < nq) {
+        out[j] = v[q];
+        found[j] = v[q] != -1;
+      }
+    }
   }
 }
 
 extern "C" int pw_ht_build(const void* klo, const void* khi, const void* vals,
-                           int64_t m, void* tab_lo, void* tab_hi,
-                           void* tab_val, int64_t nslots, void* stream) {
+                           int64_t m, void* tab, int64_t nslots,
+                           void* stream) {
   hipStream_t s = (hipStream_t)stream;
   int64_t nblocks = (m + PW_BLOCK - 1) / PW_BLOCK;
   if (nblocks > 4096) nblocks = 4096;
   if (nblocks < 1) nblocks = 1;
   hipLaunchKernelGGL(k_ht_build, dim3((uint32_t)nblocks), dim3(PW_BLOCK), 0, s,
                      (const int64_t*)klo, (const int64_t*)khi,
-                     (const int64_t*)vals, m, (int64_t*)tab_lo,
-                     (int64_t*)tab_hi, (long long*)tab_val, nslots - 1);
+                     (const int64_t*)vals, m, PwHt{(long long*)tab},
+                     nslots - 1);
   return (int)hipGetLastError();
 }
 
 extern "C" int pw_ht_probe(const void* qlo, const void* qhi, int64_t nq,
-                           const void* tab_lo, const void* tab_hi,
-                           const void* tab_val, int64_t nslots, void* out,
+                           const void* tab, int64_t nslots, void* out,
                            void* found, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  int64_t nblocks = (nq + PW_BLOCK - 1) / PW_BLOCK;
+  const int64_t per_block = (int64_t)PW_BLOCK * PW_HT_PROBE_Q;
+  int64_t nblocks = (nq + per_block - 1) / per_block;
   if (nblocks > 4096) nblocks = 4096;
   if (nblocks < 1) nblocks = 1;
   hipLaunchKernelGGL(k_ht_probe, dim3((uint32_t)nblocks), dim3(PW_BLOCK), 0, s,
                      (const int64_t*)qlo, (const int64_t*)qhi, nq,
-                     (const int64_t*)tab_lo, (const int64_t*)tab_hi,
-                     (const long long*)tab_val, nslots - 1, (int64_t*)out,
+                     PwHt{(long long*)tab}, nslots - 1, (int64_t*)out,
                      (bool*)found);
   return (int)hipGetLastError();
 }
 
 // ------------------------------------------------- hash table: intern --
-// Insert-or-get on the same table (layout unchanged, -1 still empty):
+// Insert-or-get on the same table (same slots, -1 still empty):
 // known keys return their stored code, the batch's distinct new keys get
 // codes base, base+1, ... in order of first occurrence by row index —
 // what StringPool.codes() assigns on the host.  Four launches, lock-free,
 // no lane ever waits on a value another lane is expected to write:
 //
 //   claim    row i linear-probes.  A slot with val >= 0 is compared by
-//            tab_lo/tab_hi (written by an earlier launch).  A slot with
+//            its key words (written by an earlier launch).  A slot with
 //            val <= -2 is pending: it encodes its claimer row r as -(r+2)
 //            and is compared against qlo[r]/qhi[r] — the batch is
-//            immutable, so a pending slot's tab_lo/tab_hi are never read.
+//            immutable, so a pending slot's key words are never read.
 //            Equal keys atomicMax the slot so the smallest row wins; an
 //            empty slot is claimed by CAS, and a lost CAS re-examines the
 //            same slot with the value the CAS returned.  A slot's key
 //            identity is fixed once claimed and slots are never emptied,
 //            so a key cannot land in two slots.  Hits store their code;
 //            pending rows store their slot and set pend[i] = 1.
-//            Plain tab_val loads may be stale within the launch; that is
+//            Plain val loads may be stale within the launch; that is
 //            harmless: a stale -1 is corrected by the CAS's return value,
 //            a stale pending value names another row with the same key,
 //            and no value >= 0 is written during the launch.
-//   count    pending row i is a winner iff tab_val[slot] == -(i+2); mark
+//   count    pending row i is a winner iff the slot's val == -(i+2); mark
 //            pend[i] = 2 and count winners per block chunk.
 //   commit   every block sums the counts of the chunks before it, then
 //            ranks its winners in row order; winner k writes the
 //            slot's key, the dictionary hash arrays at base+k,
-//            first_row[k] = i and, last, tab_val[slot] = base+k.
+//            first_row[k] = i and, last, the slot's val = base+k.
 //   resolve  the other pending rows read their slot's now-final code.
 //
 // On the all-known path count/commit/resolve only stream the n pend
@@ -2123,8 +2132,8 @@ extern "C" int pw_ht_probe(const void* qlo, const void* qhi, int64_t nq,
 // table above for a batch of nothing but new keys, far past the caches
 // for a large batch.  A caller may keep the keys it knows for certain in
 // a second, compact table of the same layout ("front", read-only here):
-// claim probes it first as k_ht_probe would and only its misses touch the
-// open table.  A key is in at most one of the two.
+// claim probes it first as k_ht_probe does (pw_ht_find) and only its misses
+// touch the open table.  A key is in at most one of the two.
 
 #define PW_HT_ERR_PROBE 1     // table full / probe bound hit
 #define PW_HT_ERR_STATE 2     // slot or claimer row out of range
@@ -2132,12 +2141,8 @@ extern "C" int pw_ht_probe(const void* qlo, const void* qhi, int64_t nq,
 
 __global__ void k_ht_intern_claim(const int64_t* __restrict__ qlo,
                                   const int64_t* __restrict__ qhi, int64_t n,
-                                  const int64_t* tab_lo, const int64_t* tab_hi,
-                                  long long* tab_val, int64_t nslots,
-                                  const int64_t* __restrict__ front_lo,
-                                  const int64_t* __restrict__ front_hi,
-                                  const long long* __restrict__ front_val,
-                                  int64_t front_nslots,
+                                  const PwHt tab, int64_t nslots,
+                                  const PwHt front, int64_t front_nslots,
                                   int64_t* __restrict__ codes,
                                   uint8_t* __restrict__ pend, long long* err) {
   const uint64_t mask = (uint64_t)(nslots - 1);
@@ -2147,14 +2152,7 @@ __global__ void k_ht_intern_claim(const int64_t* __restrict__ qlo,
   for (; i < n; i += stride) {
     const int64_t lo = qlo[i], hi = qhi[i];
     if (front_nslots) {
-      uint64_t fs = (uint64_t)lo & fmask;
-      long long fv = -1;
-      for (int64_t probes = 0; probes < front_nslots; ++probes) {
-        fv = front_val[fs];
-        if (fv < 0 || (front_lo[fs] == lo && front_hi[fs] == hi)) break;
-        fs = (fs + 1) & fmask;
-        fv = -1;
-      }
+      const long long fv = pw_ht_find(front, fmask, lo, hi, front_nslots);
       if (fv >= 0) {
         codes[i] = (int64_t)fv;
         pend[i] = 0;
@@ -2166,10 +2164,10 @@ __global__ void k_ht_intern_claim(const int64_t* __restrict__ qlo,
     int64_t out = -1;
     uint8_t p = 0;
     int e = PW_HT_ERR_PROBE;
-    long long tv = tab_val[slot];
+    long long tv = *tab.val(slot);
     for (int64_t probes = 0; probes < nslots; ++probes) {
       if (tv == -1) {
-        tv = (long long)atomicCAS((unsigned long long*)&tab_val[slot],
+        tv = (long long)atomicCAS((unsigned long long*)tab.val(slot),
                                   (unsigned long long)(long long)-1,
                                   (unsigned long long)me);
         if (tv == -1) {  // claimed
@@ -2178,7 +2176,8 @@ __global__ void k_ht_intern_claim(const int64_t* __restrict__ qlo,
         }
       }
       if (tv >= 0) {
-        if (tab_lo[slot] == lo && tab_hi[slot] == hi) {
+        const PwHtKey k = tab.key(slot);
+        if (k.lo == lo && k.hi == hi) {
           out = (int64_t)tv, e = 0;
           break;
         }
@@ -2190,14 +2189,14 @@ __global__ void k_ht_intern_claim(const int64_t* __restrict__ qlo,
         }
         if (qlo[r] == lo && qhi[r] == hi) {
           if (me > tv)
-            __hip_atomic_fetch_max(&tab_val[slot], me, __ATOMIC_RELAXED,
+            __hip_atomic_fetch_max(tab.val(slot), me, __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT);
           out = (int64_t)slot, p = 1, e = 0;
           break;
         }
       }
       slot = (slot + 1) & mask;
-      tv = tab_val[slot];
+      tv = *tab.val(slot);
     }
     if (e) atomicOr((unsigned long long*)err, (unsigned long long)e);
     codes[i] = out;
@@ -2208,7 +2207,7 @@ __global__ void k_ht_intern_claim(const int64_t* __restrict__ qlo,
 // rows [start, end) of one block, 16 rows (one pend granule) per lane
 __global__ void k_ht_intern_count(int64_t n, int64_t chunk,
                                   const int64_t* __restrict__ codes,
-                                  uint8_t* pend, const long long* tab_val,
+                                  uint8_t* pend, const PwHt tab,
                                   int64_t nslots, long long* block_counts,
                                   long long* err) {
   __shared__ int cnt;
@@ -2232,7 +2231,7 @@ __global__ void k_ht_intern_count(int64_t n, int64_t chunk,
         pend[i] = 0;
         continue;
       }
-      if (tab_val[slot] == -(long long)(i + 2)) {
+      if (*tab.val((uint64_t)slot) == -(long long)(i + 2)) {
         pend[i] = 2;
         ++local;
       }
@@ -2247,8 +2246,8 @@ __global__ void k_ht_intern_commit(
     const int64_t* __restrict__ qlo, const int64_t* __restrict__ qhi,
     int64_t n, int64_t chunk, int64_t* codes, const uint8_t* __restrict__ pend,
     const long long* __restrict__ block_counts,
-    const long long* __restrict__ base_ptr, int64_t* tab_lo, int64_t* tab_hi,
-    long long* tab_val, int64_t* pool_lo, int64_t* pool_hi, int64_t pool_cap,
+    const long long* __restrict__ base_ptr, const PwHt tab, int64_t* pool_lo,
+    int64_t* pool_hi, int64_t pool_cap,
     int64_t* first_row, long long* n_new, long long* err) {
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -2304,12 +2303,11 @@ __global__ void k_ht_intern_commit(
                  (unsigned long long)PW_HT_ERR_CAPACITY);
       } else {
         const int64_t lo = qlo[i], hi = qhi[i];
-        tab_lo[slot] = lo;
-        tab_hi[slot] = hi;
+        tab.set_key((uint64_t)slot, lo, hi);
         pool_lo[code] = lo;
         pool_hi[code] = hi;
         first_row[k] = i;  // k < winners <= n
-        tab_val[slot] = code;
+        *tab.val((uint64_t)slot) = code;
         codes[i] = code;
       }
       ++k;
@@ -2322,7 +2320,7 @@ __global__ void k_ht_intern_commit(
 
 __global__ void k_ht_intern_resolve(int64_t n, int64_t chunk, int64_t* codes,
                                     const uint8_t* __restrict__ pend,
-                                    const long long* __restrict__ tab_val) {
+                                    const PwHt tab) {
   int64_t start = (int64_t)blockIdx.x * chunk;
   int64_t end = min(start + chunk, n);
   for (int64_t tile = start; tile < end; tile += (int64_t)blockDim.x * 16) {
@@ -2334,7 +2332,7 @@ __global__ void k_ht_intern_resolve(int64_t n, int64_t chunk, int64_t* codes,
     }
     for (int64_t i = g; i < min(g + 16, end); ++i) {
       if (pend[i] != 1) continue;
-      long long tv = tab_val[codes[i]];
+      long long tv = *tab.val((uint64_t)codes[i]);
       codes[i] = tv >= 0 ? (int64_t)tv : -1;  // < 0 only after a flagged error
     }
   }
@@ -2349,9 +2347,7 @@ static inline int64_t pw_intern_chunk(int64_t n, int64_t nblocks) {
 // of row chunks of count/commit/resolve; block_counts has nblocks entries,
 // n_new one.
 extern "C" int pw_ht_intern(const void* qlo, const void* qhi, int64_t n,
-                            void* tab_lo, void* tab_hi, void* tab_val,
-                            int64_t nslots, const void* front_lo,
-                            const void* front_hi, const void* front_val,
+                            void* tab, int64_t nslots, const void* front,
                             int64_t front_nslots, const void* base_ptr,
                             void* pool_lo, void* pool_hi, int64_t pool_cap,
                             void* codes, void* pend, void* first_row,
@@ -2364,28 +2360,26 @@ extern "C" int pw_ht_intern(const void* qlo, const void* qhi, int64_t n,
   int64_t cblocks = (n + PW_BLOCK - 1) / PW_BLOCK;
   if (cblocks > 4096) cblocks = 4096;
   int64_t chunk = pw_intern_chunk(n, nblocks);
+  const PwHt t{(long long*)tab};
+  const PwHt f{(long long*)const_cast<void*>(front)};  // only read
   hipLaunchKernelGGL(k_ht_intern_claim, dim3((uint32_t)cblocks),
                      dim3(PW_BLOCK), 0, s, (const int64_t*)qlo,
-                     (const int64_t*)qhi, n, (const int64_t*)tab_lo,
-                     (const int64_t*)tab_hi, (long long*)tab_val, nslots,
-                     (const int64_t*)front_lo, (const int64_t*)front_hi,
-                     (const long long*)front_val, front_nslots,
+                     (const int64_t*)qhi, n, t, nslots, f, front_nslots,
                      (int64_t*)codes, (uint8_t*)pend, (long long*)err);
   hipLaunchKernelGGL(k_ht_intern_count, dim3((uint32_t)nblocks),
                      dim3(PW_BLOCK), 0, s, n, chunk, (const int64_t*)codes,
-                     (uint8_t*)pend, (const long long*)tab_val, nslots,
-                     (long long*)block_counts, (long long*)err);
+                     (uint8_t*)pend, t, nslots, (long long*)block_counts,
+                     (long long*)err);
   hipLaunchKernelGGL(k_ht_intern_commit, dim3((uint32_t)nblocks),
                      dim3(PW_BLOCK), 0, s, (const int64_t*)qlo,
                      (const int64_t*)qhi, n, chunk, (int64_t*)codes,
                      (const uint8_t*)pend, (const long long*)block_counts,
-                     (const long long*)base_ptr, (int64_t*)tab_lo,
-                     (int64_t*)tab_hi, (long long*)tab_val, (int64_t*)pool_lo,
+                     (const long long*)base_ptr, t, (int64_t*)pool_lo,
                      (int64_t*)pool_hi, pool_cap, (int64_t*)first_row,
                      (long long*)n_new, (long long*)err);
   hipLaunchKernelGGL(k_ht_intern_resolve, dim3((uint32_t)nblocks),
                      dim3(PW_BLOCK), 0, s, n, chunk, (int64_t*)codes,
-                     (const uint8_t*)pend, (const long long*)tab_val);
+                     (const uint8_t*)pend, t);
   return (int)hipGetLastError();
 }
 
