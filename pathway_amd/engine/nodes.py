@@ -45,7 +45,7 @@ from pathway_amd.engine.column import (
     concat_columns,
 )
 from pathway_amd.engine.expression_eval import EvalContext, evaluate
-from pathway_amd.engine.reducers import REDUCERS, ReducerSpec
+from pathway_amd.engine.reducers import REDUCERS, ReducerSpec, dd_add
 from pathway_amd.engine.state import (
     Arrangement,
     consolidate_sorted,
@@ -102,6 +102,13 @@ _PW_NO_MULTISET_DEVICE = bool(_os.environ.get("PW_NO_MULTISET_DEVICE"))
 #: columns — default ON; PW_NO_CONSOLIDATE_FUSED=1 forces the hash / sort /
 #: gather / seg-reduce chain (A/B)
 _PW_NO_CONSOLIDATE_FUSED = bool(_os.environ.get("PW_NO_CONSOLIDATE_FUSED"))
+
+#: float sums and averages of a GPU group reduce as double-double (hi, lo)
+#: pairs: the batch through ops.group_combine_mixed_gpu (pw_seg_sum_f64, no
+#: float atomics), the state merge through reducers.dd_add — default ON;
+#: PW_NO_F64_COMBINE=1 keeps one float64 per group, summed by the torch
+#: sort / index_add_ chain (A/B)
+_PW_NO_F64_COMBINE = bool(_os.environ.get("PW_NO_F64_COMBINE"))
 
 #: returned by GroupReduceNode._group_update when the step is not its kind
 _NOT_FUSED = object()
@@ -772,6 +779,54 @@ class GroupReduceNode(Node):
                     n: c.take(gfirst_rows) for n, c in gcols.items()
                 }
                 hashagg = True
+            f64_names = [
+                nm for nm, c in contribs.items() if c.dtype == torch.float64
+            ]
+            dd = (
+                hashagg is None
+                and bool(f64_names)
+                and self._dd_sums()
+                and all(
+                    c.dtype in (torch.int64, torch.float64)
+                    for c in contribs.values()
+                )
+            )
+            if dd and gkeys.shape[0] == 1:
+                # one row: its own group, (value, 0.0)
+                ukeys_w = [gkeys[:, 0].contiguous(), gkeys[:, 1].contiguous()]
+                acc_deltas = dict(contribs)
+                for nm in f64_names:
+                    acc_deltas[f"{nm}__c"] = torch.zeros_like(contribs[nm])
+                gcols_first = {
+                    n: c.take(torch.zeros(1, dtype=torch.int64, device=device))
+                    for n, c in gcols.items()
+                }
+                hashagg = True
+            elif dd and len(contribs) <= 8 and gkeys.shape[0] < 2**32:
+                # int64 sums as in the combiner above, float64 sums as
+                # double-doubles through the same permutation (pw_gc_* +
+                # pw_seg_sum_f64); at any batch size, since lex_sort_words
+                # does not keep equal keys in row order
+                from pathway_amd import ops
+
+                int_names = [nm for nm in contribs if nm not in f64_names]
+                uk0, uk1, gfirst_rows, accs, f_hi, f_lo = (
+                    ops.group_combine_mixed_gpu(
+                        gkeys,
+                        [contribs[nm] for nm in int_names],
+                        [contribs[nm] for nm in f64_names],
+                    )
+                )
+                ops.f64_combine_counts["native"] += 1
+                ukeys_w = [uk0, uk1]
+                acc_deltas = dict(zip(int_names, accs))
+                for nm, h, l in zip(f64_names, f_hi, f_lo):
+                    acc_deltas[nm] = h
+                    acc_deltas[f"{nm}__c"] = l
+                gcols_first = {
+                    n: c.take(gfirst_rows) for n, c in gcols.items()
+                }
+                hashagg = True
             if hashagg is None:
                 # sort path: ONE lex sort of the batch's group keys, then
                 # segmented sums per additive accumulator
@@ -811,6 +866,14 @@ class GroupReduceNode(Node):
                         acc = seg_tot.clone()
                         acc[1:] -= seg_tot[:-1]
                     acc_deltas[name] = acc
+                if dd:
+                    # more accumulators than the combiner takes: plain
+                    # float64 sums with a low part of zero
+                    from pathway_amd import ops
+
+                    ops.f64_combine_counts["chain"] += 1
+                    for nm in f64_names:
+                        acc_deltas[f"{nm}__c"] = torch.zeros_like(acc_deltas[nm])
                 gfirst_rows = perm.index_select(0, first_idx)
                 gcols_first = {n: c.take(gfirst_rows) for n, c in gcols.items()}
 
@@ -976,6 +1039,48 @@ class GroupReduceNode(Node):
                 contribs[f"{out_name}__sum"] = v * diffs.to(torch.float64)
         return contribs
 
+    def _dd_sums(self) -> bool:
+        """Whether this node keeps its float sums as double-doubles."""
+        return (
+            torch.device(self.device).type == "cuda" and not _PW_NO_F64_COMBINE
+        )
+
+    def _dd_names(self, acc_deltas=None) -> list[str]:
+        """The float64 accumulators (high parts) of the state and of
+        `acc_deltas` on a double-double node; none elsewhere.  High and
+        low part are paired by name, `x` and `x__c`, as `avg` pairs its
+        sum by `__sum`: a float sum that a user names `x__c` beside a
+        float sum `x` would be taken for its low part."""
+        if not self._dd_sums():
+            return []
+        accs = dict(acc_deltas or {})
+        accs.update(self.add_accs)
+        return [
+            nm
+            for nm, t in accs.items()
+            if t.dtype == torch.float64 and not nm.endswith("__c")
+        ]
+
+    def restore_float_accs(self) -> None:
+        """After a snapshot restore: a double-double node gets the low
+        parts its state lacks, as zeros; any other node gets each `x__c`
+        folded into `x`."""
+        if self._dd_sums():
+            for nm in self._dd_names():
+                if f"{nm}__c" not in self.add_accs:
+                    self.add_accs[f"{nm}__c"] = torch.zeros_like(self.add_accs[nm])
+            return
+        # a low part is float64 next to a float64 `x`; an int sum that a
+        # user named `x__c` is neither and stays
+        for nm in [n for n in self.add_accs if n.endswith("__c")]:
+            hi = self.add_accs.get(nm[:-3])
+            if (
+                hi is not None
+                and hi.dtype == torch.float64
+                and self.add_accs[nm].dtype == torch.float64
+            ):
+                self.add_accs[nm[:-3]] = hi + self.add_accs.pop(nm)
+
     def _merge_state_pre(self, ukeys_w, acc_deltas, gcols_first):
         """Merge consolidated (unique sorted keys, acc deltas, group values)
         into the combined state.  Group values are key-determined, so any
@@ -995,6 +1100,12 @@ class GroupReduceNode(Node):
             self.add_carried = {
                 n: c.take(idx0.to(c._device())) for n, c in gcols_first.items()
             }
+        dd_names = self._dd_names(acc_deltas)
+        for name in dd_names:
+            # a state or delta without its low part counts as zeros
+            for accs in (self.add_accs, acc_deltas):
+                if name in accs and f"{name}__c" not in accs:
+                    accs[f"{name}__c"] = torch.zeros_like(accs[name])
         all_words = [torch.cat([s, d]) for s, d in zip(self.add_keys, ukeys_w)]
         all_accs = {}
         for name in self.add_accs:
@@ -1073,8 +1184,26 @@ class GroupReduceNode(Node):
         first_idx = starts2.nonzero(as_tuple=True)[0]
         nseg2 = int(first_idx.numel())
         merged: dict[str, torch.Tensor] = {}
+        if dd_names:
+            # state and delta hold unique keys, so a key has one entry or
+            # two (state, then delta): one elementwise double-double add
+            nall = all_words[0].shape[0]
+            second = (first_idx + 1).clamp(max=nall - 1)
+            has2 = (first_idx + 1 < nall) & ~starts2.index_select(0, second)
         for name, acc in all_accs.items():
+            if name.endswith("__c") and name[:-3] in dd_names:
+                continue
             sa = acc.index_select(0, perm2)
+            if name in dd_names:
+                sl = all_accs[f"{name}__c"].index_select(0, perm2)
+                zero = torch.zeros((), dtype=sa.dtype, device=device)
+                merged[name], merged[f"{name}__c"] = dd_add(
+                    sa.index_select(0, first_idx),
+                    sl.index_select(0, first_idx),
+                    torch.where(has2, sa.index_select(0, second), zero),
+                    torch.where(has2, sl.index_select(0, second), zero),
+                )
+                continue
             out = torch.zeros(nseg2, dtype=sa.dtype, device=device)
             out.index_add_(0, seg2, sa)
             merged[name] = out
@@ -1249,6 +1378,10 @@ class GroupReduceNode(Node):
             if spec.family == "additive":
                 if spec.name == "avg":
                     sacc = self._gather_acc(f"{out_name}__sum", add_pos, add_found)
+                    if f"{out_name}__sum__c" in self.add_accs:
+                        sacc = sacc + self._gather_acc(
+                            f"{out_name}__sum__c", add_pos, add_found
+                        )
                     c = wacc()
                     vals = sacc.to(torch.float64) / c.clamp(min=1).to(torch.float64)
                     cols[out_name] = TensorColumn(vals, dt.FLOAT)
@@ -1256,6 +1389,10 @@ class GroupReduceNode(Node):
                     cols[out_name] = TensorColumn(wacc().to(torch.int64), dt.INT)
                 else:
                     acc = self._gather_acc(out_name, add_pos, add_found)
+                    if f"{out_name}__c" in self.add_accs:
+                        acc = acc + self._gather_acc(
+                            f"{out_name}__c", add_pos, add_found
+                        )
                     odt = dt.FLOAT if acc.dtype == torch.float64 else dt.INT
                     cols[out_name] = TensorColumn(acc, odt)
             elif spec.family == "multiset":

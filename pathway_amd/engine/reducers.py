@@ -56,6 +56,27 @@ def _sum_acc(args: list[torch.Tensor], diffs: torch.Tensor) -> torch.Tensor:
     return args[0].to(torch.float64) * diffs.to(torch.float64)
 
 
+def dd_add(
+    ah: torch.Tensor, al: torch.Tensor, bh: torch.Tensor, bl: torch.Tensor
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """Elementwise double-double add (ah, al) + (bh, bl) -> (h, l) with
+    h == fl(h + l): the step of pw_seg_sum_f64 in torch (Knuth's TwoSum of
+    the high parts, the low parts added to its error, renormalised; adds
+    and subtracts only, the same bits on CPU and GPU).  The float sums'
+    state of a GPU group reduce merges with it.  Where the high part of
+    the sum is not finite, the result is that high part with l = 0."""
+    s = ah + bh
+    bb = s - ah
+    e = (ah - (s - bb)) + (bh - bb)
+    e = e + (al + bl)
+    h = s + e
+    lo = e - (h - s)
+    bad_s = ~torch.isfinite(s)
+    h = torch.where(bad_s, s, h)
+    lo = torch.where(bad_s | ~torch.isfinite(h), torch.zeros_like(lo), lo)
+    return h, lo
+
+
 REDUCERS: dict[str, ReducerSpec] = {}
 
 

@@ -700,12 +700,13 @@ def _gc_temp(lib, n: int, prefix: bool, dev) -> tuple[torch.Tensor, int]:
     return torch.empty(tbytes, dtype=torch.uint8, device=dev), tbytes
 
 
-def _group_combine_two_sorts(keys_n2, contribs):
-    """group_combine_gpu's last resort, for a batch in which more rows than
+def _gc_two_sorts(keys_n2, contribs):
+    """The combiners' last resort, for a batch in which more rows than
     the repair's `max_run` share one word0 and differ in word1: two stable
     sorts (word1, then word0), sorted copies of the contributions and
     seg_reduce_gpu.  Same result as the other paths, at several times
-    the cost."""
+    the cost.  After the result: the int64 permutation and every segment's
+    start position in it."""
     k0, k1 = keys_n2[:, 0], keys_n2[:, 1]
     perm = torch.argsort(k1, stable=True)
     perm = perm.index_select(0, torch.argsort(k0.index_select(0, perm), stable=True))
@@ -714,7 +715,8 @@ def _group_combine_two_sorts(keys_n2, contribs):
         k1.index_select(0, perm),
         [c.index_select(0, perm) for c in contribs],
     )
-    return uk0, uk1, perm.index_select(0, first_sorted), accs
+    first_row = perm.index_select(0, first_sorted)
+    return uk0, uk1, first_row, accs, perm, first_sorted
 
 
 def _gc_part_hist_entries(lib, n: int, bucket_bits: int) -> int:
@@ -920,86 +922,14 @@ def _group_combine_bucket(
     return out_k[0], out_k[1], out_first, [out_accs[a] for a in range(nacc)]
 
 
-def group_combine_gpu(
-    keys_n2: torch.Tensor,
-    contribs: Sequence[torch.Tensor],
-    *,
-    prefix_bits: int = 32,
-    max_run: int = 2048,
-    max_dirty: int = 65536,
-    full_sort: bool = False,
-    bucket: bool | None = None,
-    bucket_bits: int = GC_BUCKET_BITS,
-    table_capacity: int | None = None,
-    max_bucket_rows: int | None = None,
-    partition: bool | None = None,
-) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, list]:
-    """The groupby combiner on UNSORTED interleaved keys: (n,2) int64 keys
-    + up to 8 int64 contribution columns -> (uk0, uk1, first_row, accs)
-    with unique keys in signed lexicographic order, per-key sums and the
-    smallest input row of every key (pw_gc_*: rocPRIM sort of the top
-    `prefix_bits` of word0 with a 32-bit row-index payload read straight
-    from the interleaved rows, one gather of both words, an exact repair of
-    the rows that tie on the prefix, then a segmented reduce that reads the
-    contributions through the permutation).  One host sync (segment count
-    and the repair's overflow word in one read).
-
-    A prefix run longer than `max_run` rows, or more than `max_dirty` runs
-    to repair, overflows: the batch is redone with the 64-bit sort of word0
-    (a second sync).  `full_sort` (or PW_GC_FULL_SORT=1) takes the 64-bit
-    sort at once.  That path repairs ties on the whole of word0 under the
-    same two caps; beyond them it hands over to two full sorts.  The
-    result is the same on every path.
-
-    `bucket=True` (off by default; the groupby node turns it on, through
-    gc_bucket_scope, when its estimate of the distinct keys fits) first tries the bucket path: the
-    rows are grouped by the top `bucket_bits` of word0, then one workgroup
-    per bucket aggregates its rows in an LDS table of `table_capacity`
-    entries (a power of two, default gc_bucket_capacity(nacc)) and emits
-    its unique keys in order.  It needs no order of the n rows and has one
-    host sync too.  With `bucket_bits` <= 8 the grouping is a hand-written
-    partition (count, scan, scatter) that moves key, row index and
-    contributions into bucket order, so the aggregation reads them in
-    sequence; `partition=False` (or PW_NO_GC_PARTITION=1), and any larger
-    `bucket_bits`, sorts (prefix, row) pairs by bucket instead and gathers
-    the rows through the permutation.  `gc_bucket_layout_counts` says which.  A bucket with more than GC_BUCKET_MAX_LOAD * table_capacity
-    distinct keys or more than `max_bucket_rows` rows (default: four times
-    the even share, at least 65536) overflows, and the call goes on with
-    the prefix path as if `bucket` had not been given."""
+def _gc_sort_count(lib, keys_n2, prefix_bits, max_run, max_dirty, full_sort):
+    """The sort half of group_combine_gpu and group_combine_mixed_gpu: the
+    prefix path (sort, gather, repair, count), on overflow or `full_sort`
+    the 64-bit sort.  Returns (sorted_k (2,n), perm32, block csum, nseg),
+    or None when the 64-bit sort's repair overflowed too."""
     global gc_last_dirty_runs
-    lib = require_lib()
     n = keys_n2.shape[0]
     dev = keys_n2.device
-    nacc = len(contribs)
-    assert keys_n2.dim() == 2 and keys_n2.shape[1] == 2
-    assert keys_n2.dtype == torch.int64
-    assert 2 <= n < 2**32 and nacc <= 8
-    assert 1 <= prefix_bits <= 32 and 2 <= max_run <= 3072
-    assert 1 <= max_dirty < 2**32
-    if keys_n2.stride() != (2, 1):
-        keys_n2 = keys_n2.contiguous()
-    contribs = [c.contiguous() for c in contribs]
-    assert all(c.dtype == torch.int64 and c.shape == (n,) for c in contribs)
-    if bucket is None:
-        bucket = _gc_bucket_scope
-    if bucket and not (full_sort or _PW_GC_FULL_SORT) and n < 2**32 - 1:
-        assert 1 <= bucket_bits <= 16
-        cap = table_capacity or gc_bucket_capacity(nacc)
-        assert 2 <= cap <= gc_bucket_capacity_limit(nacc) and cap & (cap - 1) == 0
-        if max_bucket_rows is None:
-            even = -(-n // (1 << bucket_bits))
-            max_bucket_rows = max(GC_BUCKET_ROWS_FACTOR * even, GC_BUCKET_ROWS_FLOOR)
-        assert max_bucket_rows >= 1
-        if partition is None:
-            partition = not _PW_NO_GC_PARTITION
-        partition = bool(partition) and bucket_bits <= GC_PART_MAX_BITS
-        res = _group_combine_bucket(
-            lib, keys_n2, contribs, bucket_bits, cap, max_bucket_rows, partition
-        )
-        if res is not None:
-            gc_path_counts["bucket"] += 1
-            gc_bucket_layout_counts["partition" if partition else "gather"] += 1
-            return res
     sorted_k = torch.empty((2, n), dtype=torch.int64, device=dev)
     perm32 = torch.empty(n, dtype=torch.int32, device=dev)  # uint32 bits
     nblocks = (n + 255) // 256
@@ -1062,8 +992,18 @@ def group_combine_gpu(
         nseg, overflow, _ = csum_ctrl[nblocks - 1 :].tolist()
         gc_path_counts["full" if full_sort else "fallback"] += 1
         if overflow:
-            # thousands of rows share a whole word0 and differ in word1
-            return _group_combine_two_sorts(keys_n2, contribs)
+            return None
+    return sorted_k, perm32, csum, nseg
+
+
+def _gc_emit(lib, sorted_k, perm32, csum, nseg, contribs, seg_pos=None):
+    """The emit half: (uk0, uk1, first_row, accs) from the sorted keys,
+    the int64 contributions read through the permutation.  `seg_pos`
+    (nseg + 1 int64) also receives every segment's start position in
+    sorted order and the row count (pw_gc_emit_pos)."""
+    n = perm32.shape[0]
+    dev = perm32.device
+    nacc = len(contribs)
     out_k = torch.empty((2, nseg), dtype=torch.int64, device=dev)
     out_first = torch.empty(nseg, dtype=torch.int64, device=dev)
     out_accs = torch.zeros((max(nacc, 1), nseg), dtype=torch.int64, device=dev)
@@ -1073,7 +1013,7 @@ def group_combine_gpu(
     oarr = (ctypes.c_void_p * max(nacc, 1))(
         *[ctypes.c_void_p(out_accs[a].data_ptr()) for a in range(nacc)]
     )
-    rc = lib.pw_gc_emit(
+    args = [
         ctypes.c_void_p(sorted_k[0].data_ptr()),
         ctypes.c_void_p(sorted_k[1].data_ptr()),
         ctypes.c_void_p(perm32.data_ptr()),
@@ -1085,11 +1025,247 @@ def group_combine_gpu(
         ctypes.c_void_p(out_k[1].data_ptr()),
         ctypes.c_void_p(out_first.data_ptr()),
         oarr,
-        stream,
-    )
+    ]
+    if seg_pos is None:
+        rc = lib.pw_gc_emit(*args, _stream_ptr())
+    else:
+        assert seg_pos.shape == (nseg + 1,) and seg_pos.dtype == torch.int64
+        rc = lib.pw_gc_emit_pos(
+            *args, ctypes.c_void_p(seg_pos.data_ptr()), _stream_ptr()
+        )
     if rc != 0:
         raise RuntimeError(f"pw_gc_emit failed: hip error {rc}")
     return out_k[0], out_k[1], out_first, [out_accs[a] for a in range(nacc)]
+
+
+def group_combine_gpu(
+    keys_n2: torch.Tensor,
+    contribs: Sequence[torch.Tensor],
+    *,
+    prefix_bits: int = 32,
+    max_run: int = 2048,
+    max_dirty: int = 65536,
+    full_sort: bool = False,
+    bucket: bool | None = None,
+    bucket_bits: int = GC_BUCKET_BITS,
+    table_capacity: int | None = None,
+    max_bucket_rows: int | None = None,
+    partition: bool | None = None,
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, list]:
+    """The groupby combiner on UNSORTED interleaved keys: (n,2) int64 keys
+    + up to 8 int64 contribution columns -> (uk0, uk1, first_row, accs)
+    with unique keys in signed lexicographic order, per-key sums and the
+    smallest input row of every key (pw_gc_*: rocPRIM sort of the top
+    `prefix_bits` of word0 with a 32-bit row-index payload read straight
+    from the interleaved rows, one gather of both words, an exact repair of
+    the rows that tie on the prefix, then a segmented reduce that reads the
+    contributions through the permutation).  One host sync (segment count
+    and the repair's overflow word in one read).
+
+    A prefix run longer than `max_run` rows, or more than `max_dirty` runs
+    to repair, overflows: the batch is redone with the 64-bit sort of word0
+    (a second sync).  `full_sort` (or PW_GC_FULL_SORT=1) takes the 64-bit
+    sort at once.  That path repairs ties on the whole of word0 under the
+    same two caps; beyond them it hands over to two full sorts.  The
+    result is the same on every path.
+
+    `bucket=True` (off by default; the groupby node turns it on, through
+    gc_bucket_scope, when its estimate of the distinct keys fits) first tries the bucket path: the
+    rows are grouped by the top `bucket_bits` of word0, then one workgroup
+    per bucket aggregates its rows in an LDS table of `table_capacity`
+    entries (a power of two, default gc_bucket_capacity(nacc)) and emits
+    its unique keys in order.  It needs no order of the n rows and has one
+    host sync too.  With `bucket_bits` <= 8 the grouping is a hand-written
+    partition (count, scan, scatter) that moves key, row index and
+    contributions into bucket order, so the aggregation reads them in
+    sequence; `partition=False` (or PW_NO_GC_PARTITION=1), and any larger
+    `bucket_bits`, sorts (prefix, row) pairs by bucket instead and gathers
+    the rows through the permutation.  `gc_bucket_layout_counts` says which.  A bucket with more than GC_BUCKET_MAX_LOAD * table_capacity
+    distinct keys or more than `max_bucket_rows` rows (default: four times
+    the even share, at least 65536) overflows, and the call goes on with
+    the prefix path as if `bucket` had not been given."""
+    lib = require_lib()
+    n = keys_n2.shape[0]
+    nacc = len(contribs)
+    assert keys_n2.dim() == 2 and keys_n2.shape[1] == 2
+    assert keys_n2.dtype == torch.int64
+    assert 2 <= n < 2**32 and nacc <= 8
+    assert 1 <= prefix_bits <= 32 and 2 <= max_run <= 3072
+    assert 1 <= max_dirty < 2**32
+    if keys_n2.stride() != (2, 1):
+        keys_n2 = keys_n2.contiguous()
+    contribs = [c.contiguous() for c in contribs]
+    assert all(c.dtype == torch.int64 and c.shape == (n,) for c in contribs)
+    if bucket is None:
+        bucket = _gc_bucket_scope
+    if bucket and not (full_sort or _PW_GC_FULL_SORT) and n < 2**32 - 1:
+        assert 1 <= bucket_bits <= 16
+        cap = table_capacity or gc_bucket_capacity(nacc)
+        assert 2 <= cap <= gc_bucket_capacity_limit(nacc) and cap & (cap - 1) == 0
+        if max_bucket_rows is None:
+            even = -(-n // (1 << bucket_bits))
+            max_bucket_rows = max(GC_BUCKET_ROWS_FACTOR * even, GC_BUCKET_ROWS_FLOOR)
+        assert max_bucket_rows >= 1
+        if partition is None:
+            partition = not _PW_NO_GC_PARTITION
+        partition = bool(partition) and bucket_bits <= GC_PART_MAX_BITS
+        res = _group_combine_bucket(
+            lib, keys_n2, contribs, bucket_bits, cap, max_bucket_rows, partition
+        )
+        if res is not None:
+            gc_path_counts["bucket"] += 1
+            gc_bucket_layout_counts["partition" if partition else "gather"] += 1
+            return res
+    sorted_ = _gc_sort_count(
+        lib, keys_n2, prefix_bits, max_run, max_dirty, full_sort
+    )
+    if sorted_ is None:
+        # thousands of rows share a whole word0 and differ in word1
+        return _gc_two_sorts(keys_n2, contribs)[:4]
+    return _gc_emit(lib, *sorted_, contribs)
+
+
+#: rows per chunk of a long segment in pw_seg_sum_f64, and the longest
+#: segment one wave reduces on its own (profiles/float_reduce_r12.md)
+SEG_SUM_F64_CHUNK = 4096
+
+#: how the groupby node reduced a batch with float64 contributions: the
+#: mixed combiner, or the torch sort / index_add_ chain (more than 8
+#: accumulators)
+f64_combine_counts = {"native": 0, "chain": 0}
+#: how group_combine_mixed_gpu ordered the rows: one of gc_path_counts'
+#: sorts (which one, that dict says), or the two stable sorts after those
+gc_mixed_path_counts = {"sorted": 0, "two_sorts": 0}
+
+
+def seg_sum_f64_gpu(
+    perm: torch.Tensor | None,
+    seg_start: torch.Tensor,
+    hi_cols: Sequence[torch.Tensor],
+    lo_cols: Sequence[torch.Tensor] | None = None,
+) -> tuple[list, list]:
+    """Segmented double-double sums (pw_seg_sum_f64): for every segment
+    `[seg_start[s], seg_start[s+1])` of the positions of `perm`, and each of
+    1..8 float64 columns read through `perm`, the sum as a normalised
+    (hi, lo) pair.  `perm`: int32 holding uint32 bits, int64, or None for
+    the identity; its entries lie in [0, n).  `seg_start`: (nseg+1,) int64
+    on the device, ascending from 0 to n.  `lo_cols`: the low parts when
+    the inputs are double-doubles themselves.  A segment's result depends
+    only on its values in permuted order and its length; there are no
+    float atomics and no host read.  A sum whose high part is not finite
+    is that high part with lo = 0."""
+    lib = require_lib()
+    ncol = len(hi_cols)
+    assert 1 <= ncol <= 8
+    n = hi_cols[0].shape[0]
+    dev = hi_cols[0].device
+    hi_cols = [c.contiguous() for c in hi_cols]
+    assert all(c.dtype == torch.float64 and c.shape == (n,) for c in hi_cols)
+    if lo_cols is not None:
+        lo_cols = [c.contiguous() for c in lo_cols]
+        assert len(lo_cols) == ncol
+        assert all(c.dtype == torch.float64 and c.shape == (n,) for c in lo_cols)
+    assert seg_start.dtype == torch.int64 and seg_start.dim() == 1
+    assert seg_start.shape[0] >= 1 and seg_start.device == dev
+    seg_start = seg_start.contiguous()
+    nseg = seg_start.shape[0] - 1
+    if perm is None:
+        mode = 0
+    else:
+        assert perm.shape == (n,) and perm.device == dev
+        assert perm.dtype in (torch.int32, torch.int64)
+        perm = perm.contiguous()
+        mode = 1 if perm.dtype == torch.int32 else 2
+    T = SEG_SUM_F64_CHUNK
+    out = torch.empty((2 * ncol, nseg), dtype=torch.float64, device=dev)
+    out_hi = [out[2 * c] for c in range(ncol)]
+    out_lo = [out[2 * c + 1] for c in range(ncol)]
+    if nseg == 0:
+        return out_hi, out_lo
+    max_list = n // T + 1
+    max_slots = n // T + max_list
+    # ctl (2, zeroed), list (3 * max_list), desc (2 * max_slots)
+    work = torch.empty(2 + 3 * max_list + 2 * max_slots, dtype=torch.int64, device=dev)
+    work[:2].zero_()
+    parts = torch.empty((2 * ncol, max_slots), dtype=torch.float64, device=dev)
+    ptrs = lambda ts: (ctypes.c_void_p * ncol)(  # noqa: E731
+        *[ctypes.c_void_p(t.data_ptr()) for t in ts]
+    )
+    rc = lib.pw_seg_sum_f64(
+        ctypes.c_void_p(perm.data_ptr() if mode else 0),
+        ctypes.c_int(mode),
+        ctypes.c_void_p(seg_start.data_ptr()),
+        ctypes.c_int64(nseg),
+        ctypes.c_int64(n),
+        ptrs(hi_cols),
+        ptrs(lo_cols) if lo_cols is not None else None,
+        ctypes.c_int(ncol),
+        ctypes.c_int64(T),
+        ptrs(out_hi),
+        ptrs(out_lo),
+        ctypes.c_void_p(work.data_ptr()),
+        ctypes.c_void_p(work[2:].data_ptr()),
+        ctypes.c_void_p(work[2 + 3 * max_list :].data_ptr()),
+        ctypes.c_void_p(parts.data_ptr()),
+        ctypes.c_int64(max_list),
+        ctypes.c_int64(max_slots),
+        _stream_ptr(),
+    )
+    if rc != 0:
+        raise RuntimeError(f"pw_seg_sum_f64 failed: error {rc}")
+    return out_hi, out_lo
+
+
+def group_combine_mixed_gpu(
+    keys_n2: torch.Tensor,
+    contribs: Sequence[torch.Tensor],
+    f64_contribs: Sequence[torch.Tensor],
+    *,
+    prefix_bits: int = 32,
+    max_run: int = 2048,
+    max_dirty: int = 65536,
+    full_sort: bool = False,
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, list, list, list]:
+    """group_combine_gpu for a batch that also carries float64 columns:
+    (uk0, uk1, first_row, accs, f_hi, f_lo), the first four as
+    group_combine_gpu returns them for the int64 `contribs`, f_hi / f_lo
+    the per-key double-double sums of `f64_contribs` (seg_sum_f64_gpu over
+    the same permutation).  The sort paths are group_combine_gpu's, the
+    bucket path left out: every one of them keeps equal keys in ascending
+    row order, so f_hi and f_lo are the same bits on each.  One host read
+    on the prefix path (the segment count)."""
+    lib = require_lib()
+    n = keys_n2.shape[0]
+    nacc = len(contribs)
+    nf = len(f64_contribs)
+    assert keys_n2.dim() == 2 and keys_n2.shape[1] == 2
+    assert keys_n2.dtype == torch.int64
+    assert 2 <= n < 2**32 and nf >= 1 and nacc + nf <= 8
+    assert 1 <= prefix_bits <= 32 and 2 <= max_run <= 3072
+    assert 1 <= max_dirty < 2**32
+    if keys_n2.stride() != (2, 1):
+        keys_n2 = keys_n2.contiguous()
+    contribs = [c.contiguous() for c in contribs]
+    assert all(c.dtype == torch.int64 and c.shape == (n,) for c in contribs)
+    f64_contribs = [c.contiguous() for c in f64_contribs]
+    assert all(c.dtype == torch.float64 and c.shape == (n,) for c in f64_contribs)
+    sorted_ = _gc_sort_count(
+        lib, keys_n2, prefix_bits, max_run, max_dirty, full_sort
+    )
+    if sorted_ is None:
+        # the two stable sorts, with their int64 permutation
+        uk0, uk1, first_row, accs, perm, first_sorted = _gc_two_sorts(
+            keys_n2, contribs
+        )
+        seg_pos = torch.cat([first_sorted, first_sorted.new_full((1,), n)])
+        gc_mixed_path_counts["two_sorts"] += 1
+    else:
+        perm = sorted_[1]
+        seg_pos = torch.empty(sorted_[3] + 1, dtype=torch.int64, device=perm.device)
+        uk0, uk1, first_row, accs = _gc_emit(lib, *sorted_, contribs, seg_pos)
+        gc_mixed_path_counts["sorted"] += 1
+    f_hi, f_lo = seg_sum_f64_gpu(perm, seg_pos, f64_contribs)
+    return uk0, uk1, first_row, accs, f_hi, f_lo
 
 
 #: column descriptor kinds of pw_row_ident / pw_consolidate_rows

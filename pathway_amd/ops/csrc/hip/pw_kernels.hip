@@ -2556,14 +2556,19 @@ __global__ void k_gc_sort_repair(const long long* __restrict__ k0,
   }
 }
 
-// block_csum is the INCLUSIVE prefix sum of k_segred_count's block counts
+// block_csum is the INCLUSIVE prefix sum of k_segred_count's block counts.
+// POS (the mixed combiner, pw_gc_emit_pos) also writes every segment's start
+// position in sorted order to out_pos, and n to out_pos[nseg]; the int-only
+// instantiation compiles to the kernel it was before the flag.
+template <bool POS>
 __global__ void k_gc_emit(const long long* __restrict__ k0,
                           const long long* __restrict__ k1,
                           const uint32_t* __restrict__ perm32,
                           AccPtrs contribs, int nacc, int64_t n,
                           const long long* __restrict__ block_csum,
                           long long* out_k0, long long* out_k1,
-                          long long* out_first, AccPtrsMut out_accs) {
+                          long long* out_first, AccPtrsMut out_accs,
+                          long long* out_pos) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   int lane = threadIdx.x & 63;
   int flag = 0;
@@ -2591,7 +2596,9 @@ __global__ void k_gc_emit(const long long* __restrict__ k0,
     out_k0[sid] = a0;
     out_k1[sid] = a1;
     out_first[sid] = (long long)row;
+    if (POS) out_pos[sid] = i;
   }
+  if (POS && i == n - 1) out_pos[block_csum[gridDim.x - 1]] = n;
   // wave-segmented sums per accumulator; padding lanes carry the sentinel
   // -1 so a real row followed by padding still detects its run tail
   long long s = (i < n) ? sid : -1;
@@ -3676,11 +3683,12 @@ extern "C" int pw_gc_bucket_compact(const void* base, const void* bucket_start,
   return (int)hipGetLastError();
 }
 
-extern "C" int pw_gc_emit(const void* k0_sorted, const void* k1_sorted,
+template <bool POS>
+static int gc_emit_launch(const void* k0_sorted, const void* k1_sorted,
                           const void* perm32, const void** contrib_ptrs,
                           int nacc, int64_t n, const void* block_csum,
                           void* out_k0, void* out_k1, void* out_first,
-                          void** out_acc_ptrs, void* stream) {
+                          void** out_acc_ptrs, void* out_pos, void* stream) {
   if (nacc < 0 || nacc > 8 || n < 1) return 1;
   AccPtrs cp;
   AccPtrsMut op;
@@ -3690,12 +3698,38 @@ extern "C" int pw_gc_emit(const void* k0_sorted, const void* k1_sorted,
   }
   hipStream_t s = (hipStream_t)stream;
   int64_t nblocks = (n + PW_BLOCK - 1) / PW_BLOCK;
-  hipLaunchKernelGGL(k_gc_emit, dim3((uint32_t)nblocks), dim3(PW_BLOCK), 0, s,
-                     (const long long*)k0_sorted, (const long long*)k1_sorted,
-                     (const uint32_t*)perm32, cp, nacc, n,
-                     (const long long*)block_csum, (long long*)out_k0,
-                     (long long*)out_k1, (long long*)out_first, op);
+  hipLaunchKernelGGL(k_gc_emit<POS>, dim3((uint32_t)nblocks), dim3(PW_BLOCK),
+                     0, s, (const long long*)k0_sorted,
+                     (const long long*)k1_sorted, (const uint32_t*)perm32, cp,
+                     nacc, n, (const long long*)block_csum,
+                     (long long*)out_k0, (long long*)out_k1,
+                     (long long*)out_first, op, (long long*)out_pos);
   return (int)hipGetLastError();
+}
+
+extern "C" int pw_gc_emit(const void* k0_sorted, const void* k1_sorted,
+                          const void* perm32, const void** contrib_ptrs,
+                          int nacc, int64_t n, const void* block_csum,
+                          void* out_k0, void* out_k1, void* out_first,
+                          void** out_acc_ptrs, void* stream) {
+  return gc_emit_launch<false>(k0_sorted, k1_sorted, perm32, contrib_ptrs,
+                               nacc, n, block_csum, out_k0, out_k1, out_first,
+                               out_acc_ptrs, nullptr, stream);
+}
+
+// pw_gc_emit that also writes seg_pos (nseg + 1 int64): every segment's
+// start position in sorted order, then n (the mixed combiner's input to
+// pw_seg_sum_f64)
+extern "C" int pw_gc_emit_pos(const void* k0_sorted, const void* k1_sorted,
+                              const void* perm32, const void** contrib_ptrs,
+                              int nacc, int64_t n, const void* block_csum,
+                              void* out_k0, void* out_k1, void* out_first,
+                              void** out_acc_ptrs, void* seg_pos,
+                              void* stream) {
+  if (seg_pos == nullptr) return 1;
+  return gc_emit_launch<true>(k0_sorted, k1_sorted, perm32, contrib_ptrs,
+                              nacc, n, block_csum, out_k0, out_k1, out_first,
+                              out_acc_ptrs, seg_pos, stream);
 }
 
 // -------------------------------------------------- output consolidation --
@@ -4414,5 +4448,314 @@ extern "C" int pw_seg_distinct(const void* lo, const void* hi, int64_t nq,
                      (const long long*)values, m, (uint32_t)table_capacity,
                      (uint32_t)max_hold, (uint32_t)max_probe,
                      (long long*)count, (long long*)first, (int*)status);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------- segmented double-double sum --
+// Float sums of the group reduce: per segment of a permuted batch, the sum
+// of up to 8 float64 columns as a double-double (hi, lo) pair, without
+// float atomics.  The value of a segment is a function of its values in
+// permuted order and of its length alone, so that the same rows give the
+// same bits wherever they sit in the batch and whatever the grid:
+//
+//   L <= T   W(v[0..L)): lane l of a wave adds v[l], v[l+64], ... in order,
+//            then six butterfly steps (xor 1, 2, 4, 8, 16, 32) add the
+//            lanes; lane 0 holds the result.  For L <= 8 eight segments
+//            share a wave, one per aligned group of 8 lanes with three
+//            butterfly steps: the same sums, since the lanes that are
+//            left out would add (0, 0), which is exact.
+//   L >  T   the segment is listed and cut into chunks of T rows counted
+//            from its start.  k_ssf_chunk reduces one chunk per workgroup
+//            (thread t adds v[t], v[t+256], ...; butterfly per wave; the
+//            four wave results added in wave order) into a scratch slot;
+//            k_ssf_combine applies W to the segment's chunk results in
+//            chunk order.
+//
+// k_ssf_short takes 8 consecutive segments per wave: the short ones in
+// 8-lane groups at once, the others up to T one after another with the
+// whole wave, and lists the long ones (integer atomics reserve list entries
+// and chunk slots; in which order does not reach the result).  No host
+// read: list and slots are sized by n / T, the later kernels are launched
+// for that many and leave at once where nothing was listed.
+//
+// The step is Knuth's TwoSum of the high parts, the low parts added to
+// its error term, and a renormalisation: adds and subtracts only, so no
+// contraction to FMA can change it.  A sum whose high part stops being
+// finite is that high part with a low part of 0, as plain float64
+// addition would give (inf stays inf, inf - inf and NaN are NaN).
+
+struct PwDD {
+  double h, l;
+};
+
+__device__ __forceinline__ PwDD pw_dd_add(PwDD a, PwDD b) {
+  double s = a.h + b.h;
+  if (!isfinite(s)) return PwDD{s, 0.0};
+  double bb = s - a.h;
+  double e = (a.h - (s - bb)) + (b.h - bb);
+  e += a.l + b.l;
+  double h = s + e;
+  if (!isfinite(h)) return PwDD{h, 0.0};
+  return PwDD{h, e - (h - s)};
+}
+
+__device__ __forceinline__ PwDD pw_dd_xor(PwDD a, int mask) {
+  return PwDD{__shfl_xor(a.h, mask, 64), __shfl_xor(a.l, mask, 64)};
+}
+
+// own value first, so that lane 0 adds in the order the comment gives
+template <int STEPS>
+__device__ __forceinline__ PwDD pw_dd_butterfly(PwDD a) {
+#pragma unroll
+  for (int k = 0; k < STEPS; ++k) a = pw_dd_add(a, pw_dd_xor(a, 1 << k));
+  return a;
+}
+
+struct F64Ptrs {
+  const double* p[8];
+};
+struct F64PtrsMut {
+  double* p[8];
+};
+
+// PM: 0 identity, 1 uint32 permutation, 2 int64 permutation.  A row
+// outside [0, n) reads as NaN instead of out of bounds.
+template <int PM>
+__device__ __forceinline__ PwDD ssf_load(const void* perm, const double* hi,
+                                         const double* lo, int64_t i,
+                                         int64_t n) {
+  int64_t row = PM == 0   ? i
+                : PM == 1 ? (int64_t)((const uint32_t*)perm)[i]
+                          : (int64_t)((const long long*)perm)[i];
+  if ((uint64_t)row >= (uint64_t)n)
+    return PwDD{__longlong_as_double(0x7ff8000000000000LL), 0.0};
+  return PwDD{hi[row], lo ? lo[row] : 0.0};
+}
+
+__device__ __forceinline__ int64_t ssf_clamp(long long v, int64_t n) {
+  return v < 0 ? 0 : (v > n ? n : (int64_t)v);
+}
+
+#define PW_SSF_SHORT 8  // segments per wave = lanes per short segment
+
+// ctl[0]: listed segments, ctl[1]: chunk slots taken (zeroed by the caller)
+// list: (seg, first slot, chunks) per entry; desc: (seg, chunk) per slot
+template <int PM>
+__global__ void k_ssf_short(const void* perm,
+                            const long long* __restrict__ seg_start,
+                            int64_t nseg, int64_t n, F64Ptrs hi, F64Ptrs lo,
+                            int ncol, int64_t T, F64PtrsMut out_hi,
+                            F64PtrsMut out_lo, unsigned long long* ctl,
+                            long long* list, long long* desc,
+                            int64_t max_list, int64_t max_slots) {
+  int lane = threadIdx.x & 63;
+  int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  int g = lane >> 3, j = lane & 7;
+  int64_t s = wave * PW_SSF_SHORT + g;
+  int64_t b = 0, L = -1;  // L < 0: no segment
+  if (s < nseg) {
+    b = ssf_clamp(seg_start[s], n);
+    int64_t e = ssf_clamp(seg_start[s + 1], n);
+    L = e > b ? e - b : 0;
+  }
+  const PwDD zero{0.0, 0.0};
+  // short segments, one per 8-lane group
+  bool is_short = L >= 0 && L <= PW_SSF_SHORT;
+  if (__ballot(is_short)) {
+    for (int c = 0; c < ncol; ++c) {
+      PwDD v = zero;
+      if (is_short && j < L)
+        v = pw_dd_add(zero, ssf_load<PM>(perm, hi.p[c], lo.p[c], b + j, n));
+      v = pw_dd_butterfly<3>(v);
+      if (is_short && j == 0) {
+        out_hi.p[c][s] = v.h;
+        out_lo.p[c][s] = v.l;
+      }
+    }
+  }
+  // the others up to T, one after another with the whole wave
+  uint64_t mid = __ballot(j == 0 && L > PW_SSF_SHORT && L <= T);
+  while (mid) {
+    int src = __ffsll((unsigned long long)mid) - 1;
+    mid &= mid - 1;
+    int64_t sb = __shfl(b, src, 64), sL = __shfl(L, src, 64);
+    int64_t ss = wave * PW_SSF_SHORT + (src >> 3);
+    for (int c = 0; c < ncol; ++c) {
+      PwDD acc = zero;
+#pragma unroll 4
+      for (int64_t i = lane; i < sL; i += 64)
+        acc = pw_dd_add(acc, ssf_load<PM>(perm, hi.p[c], lo.p[c], sb + i, n));
+      acc = pw_dd_butterfly<6>(acc);
+      if (lane == 0) {
+        out_hi.p[c][ss] = acc.h;
+        out_lo.p[c][ss] = acc.l;
+      }
+    }
+  }
+  // long segments: list them and hand out their chunk slots
+  uint64_t lng = __ballot(j == 0 && L > T);
+  while (lng) {
+    int src = __ffsll((unsigned long long)lng) - 1;
+    lng &= lng - 1;
+    int64_t sL = __shfl(L, src, 64);
+    int64_t ss = wave * PW_SSF_SHORT + (src >> 3);
+    int64_t nch = (sL + T - 1) / T;
+    long long idx = 0, base = 0;
+    if (lane == 0) {
+      idx = (long long)atomicAdd(&ctl[0], 1ULL);
+      base = (long long)atomicAdd(&ctl[1], (unsigned long long)nch);
+    }
+    idx = __shfl(idx, 0, 64);
+    base = __shfl(base, 0, 64);
+    // cannot happen for ascending seg_start within [0, n]
+    bool fits = idx < max_list && base + nch <= max_slots;
+    if (lane == 0 && idx < max_list) {
+      list[3 * idx] = ss;
+      list[3 * idx + 1] = base;
+      list[3 * idx + 2] = fits ? nch : -1;
+    }
+    if (fits) {
+      for (int64_t k = lane; k < nch; k += 64) {
+        desc[2 * (base + k)] = ss;
+        desc[2 * (base + k) + 1] = k;
+      }
+    } else if (lane == 0 && idx >= max_list) {
+      for (int c = 0; c < ncol; ++c) {
+        out_hi.p[c][ss] = __longlong_as_double(0x7ff8000000000000LL);
+        out_lo.p[c][ss] = 0.0;
+      }
+    }
+  }
+}
+
+// parts: (2 * ncol, max_slots) doubles: hi and lo row of every column
+template <int PM>
+__global__ void k_ssf_chunk(const void* perm,
+                            const long long* __restrict__ seg_start,
+                            int64_t nseg, int64_t n, F64Ptrs hi, F64Ptrs lo,
+                            int ncol, int64_t T,
+                            const unsigned long long* __restrict__ ctl,
+                            const long long* __restrict__ desc, double* parts,
+                            int64_t max_slots) {
+  int64_t slot = blockIdx.x;
+  unsigned long long taken = ctl[1];
+  if (slot >= max_slots || (unsigned long long)slot >= taken) return;
+  int64_t s = desc[2 * slot], k = desc[2 * slot + 1];
+  if (s < 0 || s >= nseg || k < 0 || k > n / T) return;
+  int64_t b0 = ssf_clamp(seg_start[s], n), e0 = ssf_clamp(seg_start[s + 1], n);
+  int64_t b = b0 + k * T;
+  int64_t e = b + T < e0 ? b + T : e0;
+  int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  __shared__ PwDD wave_sum[PW_BLOCK / 64];
+  const PwDD zero{0.0, 0.0};
+  for (int c = 0; c < ncol; ++c) {
+    PwDD acc = zero;
+#pragma unroll 4
+    for (int64_t i = b + threadIdx.x; i < e; i += PW_BLOCK)
+      acc = pw_dd_add(acc, ssf_load<PM>(perm, hi.p[c], lo.p[c], i, n));
+    acc = pw_dd_butterfly<6>(acc);
+    if (lane == 0) wave_sum[wv] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      PwDD r = wave_sum[0];
+      for (int w = 1; w < PW_BLOCK / 64; ++w) r = pw_dd_add(r, wave_sum[w]);
+      parts[(size_t)(2 * c) * max_slots + slot] = r.h;
+      parts[(size_t)(2 * c + 1) * max_slots + slot] = r.l;
+    }
+    __syncthreads();
+  }
+}
+
+__global__ void k_ssf_combine(int64_t nseg, int ncol,
+                              const unsigned long long* __restrict__ ctl,
+                              const long long* __restrict__ list,
+                              const double* __restrict__ parts,
+                              int64_t max_list, int64_t max_slots,
+                              F64PtrsMut out_hi, F64PtrsMut out_lo) {
+  int lane = threadIdx.x & 63;
+  int64_t idx = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  unsigned long long listed = ctl[0];
+  if (idx >= max_list || (unsigned long long)idx >= listed) return;
+  int64_t s = list[3 * idx], base = list[3 * idx + 1], nch = list[3 * idx + 2];
+  if (s < 0 || s >= nseg) return;
+  const PwDD zero{0.0, 0.0};
+  for (int c = 0; c < ncol; ++c) {
+    PwDD acc = zero;
+    if (nch < 0) acc.h = __longlong_as_double(0x7ff8000000000000LL);
+    const double* ph = parts + (size_t)(2 * c) * max_slots + base;
+    const double* pl = parts + (size_t)(2 * c + 1) * max_slots + base;
+    for (int64_t k = lane; k < nch; k += 64)
+      acc = pw_dd_add(acc, PwDD{ph[k], pl[k]});
+    acc = pw_dd_butterfly<6>(acc);
+    if (lane == 0) {
+      out_hi.p[c][s] = acc.h;
+      out_lo.p[c][s] = acc.l;
+    }
+  }
+}
+
+template <int PM>
+static void ssf_launch(const void* perm, const long long* seg_start,
+                       int64_t nseg, int64_t n, F64Ptrs hp, F64Ptrs lp,
+                       int ncol, int64_t T, F64PtrsMut oh, F64PtrsMut ol,
+                       unsigned long long* ctl, long long* list,
+                       long long* desc, double* parts, int64_t max_list,
+                       int64_t max_slots, hipStream_t s) {
+  int64_t waves = (nseg + PW_SSF_SHORT - 1) / PW_SSF_SHORT;
+  int64_t blocks = (waves * 64 + PW_BLOCK - 1) / PW_BLOCK;
+  hipLaunchKernelGGL(k_ssf_short<PM>, dim3((uint32_t)blocks), dim3(PW_BLOCK),
+                     0, s, perm, seg_start, nseg, n, hp, lp, ncol, T, oh, ol,
+                     ctl, list, desc, max_list, max_slots);
+  if (n <= T) return;  // no segment can be long
+  hipLaunchKernelGGL(k_ssf_chunk<PM>, dim3((uint32_t)max_slots),
+                     dim3(PW_BLOCK), 0, s, perm, seg_start, nseg, n, hp, lp,
+                     ncol, T, ctl, desc, parts, max_slots);
+  int64_t cblocks = (max_list * 64 + PW_BLOCK - 1) / PW_BLOCK;
+  hipLaunchKernelGGL(k_ssf_combine, dim3((uint32_t)cblocks), dim3(PW_BLOCK), 0,
+                     s, nseg, ncol, ctl, list, parts, max_list, max_slots, oh,
+                     ol);
+}
+
+// perm: n row indices (perm_mode 1: uint32, 2: int64) or unused (0:
+// identity).  seg_start: nseg + 1 int64, ascending, from 0 to n.  hi_ptrs:
+// ncol float64 columns of n; lo_ptrs: null, or their low parts.  out_hi,
+// out_lo: ncol columns of nseg.  ctl: 2 uint64, ZEROED by the caller.
+// list: 3 * max_list int64, desc: 2 * max_slots int64, parts: 2 * ncol *
+// max_slots float64, with max_list >= n / T + 1 and max_slots >= n / T +
+// max_list (a long segment of L rows takes ceil(L / T) < L / T + 1 slots).
+extern "C" int pw_seg_sum_f64(const void* perm, int perm_mode,
+                              const void* seg_start, int64_t nseg, int64_t n,
+                              const void** hi_ptrs, const void** lo_ptrs,
+                              int ncol, int64_t T, void** out_hi,
+                              void** out_lo, void* ctl, void* list, void* desc,
+                              void* parts, int64_t max_list, int64_t max_slots,
+                              void* stream) {
+  if (ncol < 1 || ncol > 8 || nseg < 0 || n < 0) return 1;
+  if (perm_mode < 0 || perm_mode > 2 || (perm_mode && !perm)) return 1;
+  if (T < 64 || T > ((int64_t)1 << 24)) return 1;
+  if (max_list < n / T + 1 || max_slots < n / T + max_list) return 1;
+  if (max_slots >= ((int64_t)1 << 31)) return 1;
+  if (nseg == 0) return 0;
+  F64Ptrs hp, lp;
+  F64PtrsMut oh, ol;
+  for (int c = 0; c < 8; ++c) {
+    hp.p[c] = c < ncol ? (const double*)hi_ptrs[c] : nullptr;
+    lp.p[c] = (c < ncol && lo_ptrs) ? (const double*)lo_ptrs[c] : nullptr;
+    oh.p[c] = c < ncol ? (double*)out_hi[c] : nullptr;
+    ol.p[c] = c < ncol ? (double*)out_lo[c] : nullptr;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (perm_mode == 0)
+    ssf_launch<0>(perm, (const long long*)seg_start, nseg, n, hp, lp, ncol, T,
+                  oh, ol, (unsigned long long*)ctl, (long long*)list,
+                  (long long*)desc, (double*)parts, max_list, max_slots, s);
+  else if (perm_mode == 1)
+    ssf_launch<1>(perm, (const long long*)seg_start, nseg, n, hp, lp, ncol, T,
+                  oh, ol, (unsigned long long*)ctl, (long long*)list,
+                  (long long*)desc, (double*)parts, max_list, max_slots, s);
+  else
+    ssf_launch<2>(perm, (const long long*)seg_start, nseg, n, hp, lp, ncol, T,
+                  oh, ol, (unsigned long long*)ctl, (long long*)list,
+                  (long long*)desc, (double*)parts, max_list, max_slots, s);
   return (int)hipGetLastError();
 }

@@ -407,6 +407,9 @@ def node_state_load(node, state, device) -> None:
         node.add_accs = {
             n: tensor_from_portable(t, device) for n, t in state["add_accs"].items()
         }
+        # the low parts (`x__c`) of double-double float sums: created or
+        # folded away to suit the node restored into
+        node.restore_float_accs()
         node.add_carried = {
             n: column_from_portable(c, device) for n, c in state["add_carried"].items()
         }
