@@ -30,6 +30,14 @@ def _topk(scores: torch.Tensor, k: int) -> tuple[torch.Tensor, torch.Tensor]:
     return torch.topk(scores, min(k, scores.shape[1]), dim=1)
 
 
+def _valid_hits(top_scores: torch.Tensor, top_idx: torch.Tensor) -> torch.Tensor:
+    """Slots of a _topk result that hold a candidate.  Dead and padded
+    candidates are masked to -inf before the selection: torch.topk returns
+    them as -inf with some index, the HIP kernel leaves the slot unfilled
+    as (-inf, -1).  Neither is a hit."""
+    return (top_scores > float("-inf")) & (top_idx >= 0)
+
+
 class FlatIndexState:
     """GPU brute-force index with device-side tombstone deletion.
 
@@ -142,8 +150,7 @@ class FlatIndexState:
         ids = self.keys.index_select(0, top_idx.reshape(-1).clamp(min=0)).reshape(
             nq, kk, 2
         )
-        valid = top_scores > float("-inf")
-        return ids, top_scores, valid
+        return ids, top_scores, _valid_hits(top_scores, top_idx)
 
 
 class IvfFlatState(FlatIndexState):
@@ -374,8 +381,7 @@ class IvfFlatState(FlatIndexState):
         ids = self.keys.index_select(0, top_rows.reshape(-1).clamp(min=0)).reshape(
             nq, kk, 2
         )
-        valid = top_scores > float("-inf")
-        return ids, top_scores, valid
+        return ids, top_scores, _valid_hits(top_scores, top_pos)
 
 
 class LshState(FlatIndexState):
@@ -492,5 +498,4 @@ class LshState(FlatIndexState):
         ids = self.keys.index_select(0, top_rows.reshape(-1).clamp(min=0)).reshape(
             nq, kk, 2
         )
-        valid = top_scores > float("-inf")
-        return ids, top_scores, valid
+        return ids, top_scores, _valid_hits(top_scores, top_pos)

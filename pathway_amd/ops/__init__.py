@@ -452,7 +452,13 @@ def hash_agg_gpu(
     estimate is vocabulary-scale — the round-1 A/B lost because the 2n
     table was a 270 MB HBM random walk).  Returns None if the estimate
     was too small (probe-chain overflow): redo on the sort path with a
-    bigger estimate."""
+    bigger estimate.
+
+    Limits: at most 8 accumulators; k0 == INT64_MIN is the table's empty
+    mark and must not occur; and since the table's second words start at
+    0, a row with k1 == 0 can be added to a slot that another key with
+    the same k0 has claimed but not yet published.  Keys are 128-bit
+    hashes, so neither happens in practice."""
     lib = require_lib()
     n = k0.shape[0]
     dev = k0.device
@@ -519,12 +525,20 @@ def seg_reduce_words_gpu(
     """Fused segmented reduce over rows SORTED by `words` (≤8 int64 word
     columns): returns (unique word columns, first_row_idx, [per-seg int64
     sums...]) — the whole run-starts/compaction/segment-sum chain in two
-    kernels + one tiny cumsum."""
+    kernels + one tiny cumsum.  At most 8 accumulators; sums wrap modulo
+    2^64.  No rows in, no rows out."""
     lib = require_lib()
     n = words[0].shape[0]
     dev = words[0].device
     nw = len(words)
     nacc = len(contribs)
+    if nw > 8 or nacc > 8:
+        raise RuntimeError(
+            f"seg_reduce_words_gpu: {nw} words, {nacc} accumulators (8 at the most)"
+        )
+    if n == 0:
+        empty = lambda: torch.empty(0, dtype=torch.int64, device=dev)  # noqa: E731
+        return [empty() for _ in range(nw)], empty(), [empty() for _ in range(nacc)]
     words = [w.contiguous() for w in words]
     nblocks = (n + 255) // 256
     block_counts = torch.empty(nblocks, dtype=torch.int32, device=dev)
@@ -1521,6 +1535,8 @@ def gemm_bias_act_gpu(
     N, K2 = b_t.shape
     assert K == K2
     out = torch.empty((M, N), dtype=torch.bfloat16, device=a.device)
+    if M == 0 or N == 0:
+        return out  # nothing to compute, and a grid of no blocks is an error
     if bias is not None:
         bias = bias.to(torch.float32).contiguous()
     act_code = {"none": 0, "gelu": 1}[act]
@@ -1543,7 +1559,11 @@ def gemm_bias_act_gpu(
 def topk_gpu(scores: torch.Tensor, k: int) -> tuple[torch.Tensor, torch.Tensor]:
     """Per-row top-k (higher=better) via the hand-written HIP kernel.
 
-    scores (nq, m) float32 -> (vals (nq, k) f32, idx (nq, k) int64).
+    scores (nq, m) float32 -> (vals (nq, k) f32, idx (nq, k) int64),
+    1 <= k <= 32, values non-increasing along a row.  A row with fewer
+    than k scores above -inf leaves its last slots unfilled: (-inf, -1),
+    the value torch.topk gives such a slot and an index no row has.  NaN
+    scores are never selected.  Equal scores rank in no defined order.
     """
     lib = require_lib()
     nq, m = scores.shape
@@ -1949,7 +1969,12 @@ def sort_repair_gpu(
 ) -> None:
     """In-place odd-even repair of word1 order inside equal-word0 runs
     (k_sort_repair) — the sync-free replacement for the 2-word sort fast
-    path's collision check.  Mutates k1_sorted and perm."""
+    path's collision check.  Mutates k1_sorted and perm.
+
+    Contract: every equal-word0 run of up to `passes` rows ends up in
+    ascending word1 order (odd-even transposition needs as many passes as
+    the run has rows); a longer run may stay partly unordered.  The default
+    of 4 repairs runs of up to 4 rows."""
     lib = require_lib()
     n = k0_sorted.shape[0]
     if n < 2:

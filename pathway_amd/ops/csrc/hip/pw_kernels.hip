@@ -777,7 +777,12 @@ __global__ __launch_bounds__(256) void k_gemm_bf16(
   bool interior_mn = (row0 + PW_GEMM_BM <= M) && (col0 + PW_GEMM_BN <= N);
 
   // fast staging for interior tiles: async global->LDS DMA, 16B per lane
-  // (guide §5: global_load_lds dwordx4 — the compiler never auto-emits it)
+  // (guide §5: global_load_lds dwordx4 — the compiler never auto-emits it).
+  // Contract: only for K % 8 == 0, where every row of A and Bt, and every
+  // 8-element chunk the DMA reads, is as aligned as the base pointer (16
+  // bytes for a whole torch allocation).  Any other K leaves rows 2-, 4- or
+  // 8-byte aligned and stages through load_tiles, whose vector loads fall
+  // back to element loads at the K tail.
   auto load_tiles_gll = [&](int kt, int buf) {
     int64_t k0 = (int64_t)kt * PW_GEMM_BK;
     // A tile: 16 KiB = 16 wave-chunks of 1 KiB; 4 chunks per wave
@@ -840,7 +845,7 @@ __global__ __launch_bounds__(256) void k_gemm_bf16(
   };
 
   auto stage = [&](int kt, int buf) {
-    if (interior_mn && (int64_t)(kt + 1) * PW_GEMM_BK <= K)
+    if (interior_mn && (K & 7) == 0 && (int64_t)(kt + 1) * PW_GEMM_BK <= K)
       load_tiles_gll(kt, buf);
     else
       load_tiles(kt, buf);
@@ -932,13 +937,19 @@ extern "C" int pw_gemm_bf16(const void* A, const void* B, const void* bias,
 // replaces torch.topk on the query path).  One block per query; each
 // thread keeps a k-deep insertion list over its strided slice, lists are
 // merged in LDS by k selection passes.  k <= 32.
+//
+// The "empty" value is -inf, as torch.topk would value a missing
+// candidate: a slot the row could not fill (fewer than k scores above
+// -inf) is written (-inf, -1).  Every comparison is a strict `>`, so a
+// -inf or NaN score is never inserted or selected, and every finite score
+// down to float32 lowest can be.  Equal scores rank in no defined order.
 
 #define PW_TOPK_MAXK 32
 
 __global__ __launch_bounds__(256) void k_topk(
     const float* __restrict__ scores, int64_t m, int k,
     float* __restrict__ out_vals, int64_t* __restrict__ out_idx) {
-  const float NEG = -3.4e38f;
+  const float NEG = -INFINITY;
   __shared__ float svals[256 * PW_TOPK_MAXK];
   __shared__ int sidx[256 * PW_TOPK_MAXK];
   int64_t q = blockIdx.x;
@@ -996,7 +1007,8 @@ __global__ __launch_bounds__(256) void k_topk(
         }
       }
       if (tid == 0) {
-        if (bestpos >= 0 && best > NEG) {
+        // bestpos >= 0 only for a candidate above -inf (strict `>` above)
+        if (bestpos >= 0) {
           out_vals[q * k + sel] = best;
           out_idx[q * k + sel] = sidx[bestpos];
           svals[bestpos] = NEG;
@@ -1855,10 +1867,13 @@ extern "C" int pw_scan_emit(const void* buf, int64_t n, int target,
 // After the 2-word fast-path sort by word0 only, rows in an equal-word0
 // run may be out of order on word1.  Host-sync-checking for collisions
 // cost 0.27 ms/step (10 syncs); instead: odd-even transposition passes
-// restricted to equal-k0 pairs, entirely on device.  `passes` bounds the
-// repairable run length; 64-bit hash keys make runs >8 over any real
-// row count astronomically improbable (n^9 / 2^512).  Signed compare
-// matches torch.sort / the multi-pass fallback.
+// restricted to equal-k0 pairs, entirely on device.  Contract: odd-even
+// transposition sorts a run of L rows in L passes (wherever the run
+// starts), so a call repairs every run of up to `passes` rows and may
+// leave a longer one partly ordered.  The wrapper's default is 4 passes:
+// with 64-bit hash keys a run of 5 needs five rows to share word0, about
+// n^5 / 2^256 over n rows.  Signed compare matches torch.sort / the
+// multi-pass fallback.
 
 __global__ void k_sort_repair(const long long* __restrict__ k0,
                               long long* k1, long long* perm, int64_t n,
