@@ -59,14 +59,32 @@ def _stream_ptr() -> ctypes.c_void_p:
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+#: widest row k_hash128_words is instantiated for
+HASH_MAX_WORDS = 20
+
+
 def hash128_words_gpu(words: Sequence[torch.Tensor]) -> tuple[torch.Tensor, torch.Tensor]:
-    """Fused device 128-bit hash of rows of int64 words."""
+    """Fused device 128-bit hash of rows of int64 words: 1 to HASH_MAX_WORDS
+    1-D int64 tensors of one length on one device."""
     lib = require_lib()
+    if not 1 <= len(words) <= HASH_MAX_WORDS:
+        raise ValueError(
+            f"hash128_words_gpu takes 1..{HASH_MAX_WORDS} words, got {len(words)}"
+        )
     n = words[0].shape[0]
+    for w in words:
+        if w.dtype != torch.int64:
+            raise ValueError(f"hash128_words_gpu needs int64 words, got {w.dtype}")
+        if w.dim() != 1 or w.shape[0] != n:
+            raise ValueError("hash128_words_gpu needs 1-D words of one length")
+        if w.device != words[0].device:
+            raise ValueError("hash128_words_gpu needs all words on one device")
     lo = torch.empty(n, dtype=torch.int64, device=words[0].device)
     hi = torch.empty(n, dtype=torch.int64, device=words[0].device)
+    # the contiguous copies stay referenced until the launch is queued
+    words = [w.contiguous() for w in words]
     arr = (ctypes.c_void_p * len(words))(
-        *[ctypes.c_void_p(w.contiguous().data_ptr()) for w in words]
+        *[ctypes.c_void_p(w.data_ptr()) for w in words]
     )
     rc = lib.pw_hash128_words(
         arr,
@@ -1493,17 +1511,34 @@ def consolidate_rows_gpu(
     return out_rows[:total], out_w[:total]
 
 
+#: blocks of k_partition_count / k_partition_scatter at the most; each owns
+#: one contiguous chunk of rows
+PART_MAX_BLOCKS = 2048
+
+
 def partition_gpu(dest: torch.Tensor, world: int) -> tuple[torch.Tensor, torch.Tensor]:
     """Radix partition by destination rank: returns (perm, counts) with rows
-    grouped by destination (exchange shuffle pack; pact.rs:56 analog)."""
+    grouped by destination (exchange shuffle pack; pact.rs:56 analog).
+
+    dest is a 1-D int64 tensor and 1 <= world <= 64.  Every dest[i] must lie
+    in [0, world): the kernels index a world-sized histogram with it
+    unchecked, so a value outside that range is the caller's error.  The
+    order of rows inside one destination is unspecified."""
     lib = require_lib()
+    if world < 1:
+        raise ValueError(f"partition_gpu needs world >= 1, got {world}")
+    if dest.dtype != torch.int64:
+        raise ValueError(f"partition_gpu needs int64 destinations, got {dest.dtype}")
+    if dest.dim() != 1:
+        raise ValueError(f"partition_gpu needs 1-D destinations, got {dest.dim()}-D")
     n = dest.shape[0]
-    nblocks = max(1, min(2048, (n + 255) // 256))
+    nblocks = max(1, min(PART_MAX_BLOCKS, (n + 255) // 256))
     perm = torch.empty(n, dtype=torch.int64, device=dest.device)
     counts = torch.empty(world, dtype=torch.int64, device=dest.device)
     scratch = torch.empty(nblocks * world, dtype=torch.int64, device=dest.device)
+    dest = dest.contiguous()
     rc = lib.pw_partition(
-        ctypes.c_void_p(dest.contiguous().data_ptr()),
+        ctypes.c_void_p(dest.data_ptr()),
         ctypes.c_int64(n),
         ctypes.c_int(world),
         ctypes.c_void_p(perm.data_ptr()),
@@ -1852,6 +1887,14 @@ def group_update_gpu(
     return out_words, out_accs, rep, keys, diffs, [vals[s] for s in slots], src
 
 
+#: radix sort geometry: one wave of RS_LANES lanes per block, each lane a
+#: contiguous chunk; RS_BLOCK_ROWS rows per block until RS_MAX_BLOCKS
+#: blocks, longer chunks from there on
+RS_LANES = 64
+RS_BLOCK_ROWS = 64 * RS_LANES
+RS_MAX_BLOCKS = 1024
+
+
 def radix_sort64_gpu(keys: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     """Hand-written LSD radix sort of int64 keys (signed order).
 
@@ -1865,14 +1908,15 @@ def radix_sort64_gpu(keys: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     perm = torch.arange(n, dtype=torch.int64, device=device)
     if n <= 1:
         return keys.clone(), perm
-    nblocks = max(1, min(1024, (n + (64 * 64) - 1) // (64 * 64)))
-    chunk = (n + nblocks * 64 - 1) // (nblocks * 64)
+    nblocks = max(1, min(RS_MAX_BLOCKS, (n + RS_BLOCK_ROWS - 1) // RS_BLOCK_ROWS))
+    chunk = (n + nblocks * RS_LANES - 1) // (nblocks * RS_LANES)
     ka = torch.empty(n, dtype=torch.int64, device=device)  # uint64 bits
     kb = torch.empty(n, dtype=torch.int64, device=device)
     pa = perm
     pb = torch.empty(n, dtype=torch.int64, device=device)
+    keys = keys.contiguous()
     rc = lib.pw_radix_flip(
-        ctypes.c_void_p(keys.contiguous().data_ptr()),
+        ctypes.c_void_p(keys.data_ptr()),
         ctypes.c_void_p(ka.data_ptr()),
         ctypes.c_int64(n),
         _stream_ptr(),
@@ -2259,10 +2303,19 @@ class DeviceHashTable:
         return out, found
 
 
+#: gather_all takes the fused kernel above this many index rows
+GATHER_ALL_MIN_ROWS = 2048
+
+
 def gather_all(idx: torch.Tensor, tensors: list) -> list:
     """Gather a list of same-length tensors through one index — fused
     k_gather_cols on device, per-tensor index_select elsewhere."""
-    if tensors and tensors[0].is_cuda and idx.shape[0] > 2048 and lib_available():
+    if (
+        tensors
+        and tensors[0].is_cuda
+        and idx.shape[0] > GATHER_ALL_MIN_ROWS
+        and lib_available()
+    ):
         return gather_cols_gpu(idx, list(tensors))
     return [
         t.index_select(0, idx) if t.dim() == 1 else t[idx] for t in tensors
